@@ -2,14 +2,19 @@
 """Headline benchmark: images/sec of the ERFNet-RAP step-2 (CS->BDD, KD on) training iteration at
 1024x512, batch 6 per GPU (BASELINE.json configs[2]; train_new_task_step2.py:285-306).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = 2 student forwards (train mode, batch-stat BN, Dropout2d) + frozen teacher forward
 (eval) + weighted CE + 0.1*KLD + backward through both student graphs + RCCL all-reduce of the
 flat gradient buffer (N>1) + fused Adam, on a fresh synthetic batch already resident in HBM.
-Prints ONE JSON line (rank 0) with the throughput, the roofline of the dominant kernel (HIP-event
-timed on the launch stream) and a CPU baseline of the same iteration run by the oracle.
+Prints ONE JSON line (rank 0) with the throughput and ``ms_per_step``.  A plain run does nothing
+else: set-up, warm-up, the K timed steps, the optional output dump, the line.  ``--full`` adds the
+roofline of the dominant kernel (HIP-event timed on the launch stream, extra profiled steps) and a
+CPU baseline of the same iteration run by the oracle.
+``--dump-outputs DIR`` writes what the last timed step produced (its returned losses and the
+trained model's state after it) as DIR/<name>.npy; inputs, initial weights and dropout masks are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -208,7 +213,7 @@ def build_secondary(wl, dev, pool, streams):
     if wl == "step1":
         model = Net([20], 1, 0).to(dev)
         eng = E.Step1Engine(model, w20, 0)
-        return eng, lambda i: (eng.iteration(*pool[i % len(pool)]),)
+        return eng, lambda i: (eng.iteration(*pool[i % len(pool)]),), model
     if wl == "eval":
         from mdil_ss_amd.iouEval import iouEval
         model = Net([20, 20], 2, 1).to(dev).eval()
@@ -221,7 +226,7 @@ def build_secondary(wl, dev, pool, streams):
                 loss = ops.cross_entropy2d(out, lab[:, 0], w20)
                 meter.addBatch(out, lab)
             return (loss,)
-        return None, step
+        return None, step, model
     if wl == "multitask":
         from mdil_ss_amd.models.erfnet_multi_task import Net as NetMT
         model = NetMT([20, 20, 27], 3, 0).to(dev)
@@ -232,7 +237,7 @@ def build_secondary(wl, dev, pool, streams):
             for ind in range(3):
                 out = eng.sub_step(ind, *pool[(i + ind) % len(pool)])
             return (out,)
-        return eng, step
+        return eng, step, model
     from mdil_ss_amd import train_new_task_step3 as T3
     torch.manual_seed(1)
     teacher = Net([20, 20], 2, 1)
@@ -247,7 +252,7 @@ def build_secondary(wl, dev, pool, streams):
     T3.current_task = 2
     eng = E.Step3Engine(student, teacher, w27, current_task=2, lambdac=0.1, is_shared=T3.is_shared,
                         is_ds_curr=T3.is_DS_curr, streams=streams)
-    return eng, lambda i: eng.iteration(*pool[i % len(pool)])
+    return eng, lambda i: eng.iteration(*pool[i % len(pool)]), student
 
 
 def spawn_ranks(n):
@@ -295,6 +300,29 @@ def timed_steps(step, steps, warmup, world, sync):
     return dt, t_enq, out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, result, names, model=None):
+    """--dump-outputs: what the last timed step handed its caller -- the returned tensors (named
+    ``names``, else out0, out1, ...) and, for a training step, the model's state after the update
+    (state.<state-dict key>: parameters and BatchNorm running statistics) -- as <path>/<name>.npy,
+    float64 tensors as float64, every other one as float32."""
+    import numpy as np
+    arrays = []
+    for i, t in enumerate(result):
+        arrays.append((names[i] if i < len(names) else f"out{i}", t))
+    if model is not None:
+        arrays += [("state." + k, v) for k, v in model.state_dict().items() if v.is_floating_point()]
+    total = sum(t.numel() * (8 if t.dtype == torch.float64 else 4) for _, t in arrays)
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})"
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays:
+        a = t.detach().cpu()
+        a = a.double() if a.dtype == torch.float64 else a.float()
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+
+
 def stub_cpu(args, world, rank):
     """--stub-cpu: the same launch / barrier / max-over-ranks / one-JSON-line harness on the gloo
     backend with a stand-in step (a small matmul + a gradient-sized all-reduce)."""
@@ -310,6 +338,8 @@ def stub_cpu(args, world, rank):
             dist.all_reduce(g)
         return (g[:1].clone(),)
     dt, t_enq, out = timed_steps(step, args.steps, args.warmup, world, lambda: None)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, ("checksum",))
     if rank == 0:
         print(json.dumps({"metric": "stub steps/sec (harness self-test, not a measurement)",
                           "value": round(world * args.steps / dt, 3), "unit": "steps/sec", "n_gpus": world,
@@ -333,8 +363,13 @@ def main():
     ap.add_argument("--batch-size", type=int, default=6)
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=1024)
-    ap.add_argument("--profile-steps", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline leg "
+                         "(--profile-steps extra profiled steps) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (losses, model state) as DIR/<name>.npy")
+    ap.add_argument("--profile-steps", type=int, default=2, help="(--full) steps of the roofline leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--single-stream", action="store_true",
                     help="enqueue the three forwards / two backwards on one stream")
     ap.add_argument("--async-wgrad", action="store_true",
@@ -399,8 +434,9 @@ def main():
             img, lab = pool[i % len(pool)]
             nxt = pool[(i + 1) % len(pool)][0] if args.pipeline_teacher else None
             return eng.iteration(img, lab, nxt)
+        model = student
     else:
-        eng, step = build_secondary(wl, dev, pool, not args.single_stream)
+        eng, step, model = build_secondary(wl, dev, pool, not args.single_stream)
         args.single_stream = True if wl in ("step1", "multitask", "eval") else args.single_stream
 
     step(0)                                  # first step runs on one stream (builds weight images)
@@ -410,10 +446,14 @@ def main():
             eng.enable_graph(*pool[0])
     dt, t_enq, losses = timed_steps(step, args.steps, args.warmup, world, torch.cuda.synchronize)
     total_loss = float(losses[0])
+    if rank == 0 and args.dump_outputs:
+        # before the roofline leg's extra steps move the model on; the eval workload trains nothing
+        dump_outputs(args.dump_outputs, losses, ("loss_total", "loss_ce", "loss_kld") if wl == "step2" else (),
+                     None if wl == "eval" else model)
 
-    # ---- roofline leg: per-launch HIP-event timing of the MFMA kernels on their stream ----
+    # ---- roofline leg (--full): per-launch HIP-event timing of the MFMA kernels on their stream ----
     roof = None
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         # every rank runs the extra steps (they contain the gradient all-reduce); rank 0 reports.
         # The library brackets each conv / weight-gradient launch of the shipped call sequence
         # (block-level C ABI, deferred reductions) with HIP events on its stream (csrc/prof.cpp).
@@ -431,7 +471,7 @@ def main():
         if eng is not None:
             eng.graph, eng.multi_stream = saved
             eng.want_streams = want
-    if rank == 0 and args.profile_steps > 0 and records:
+    if rank == 0 and args.full and args.profile_steps > 0 and records:
         agg = {}
         for kind, cin, cout, ntaps, flops, sec_ in records:
             a = agg.setdefault((kind, cin, cout, ntaps), [0.0, 0.0, 0])
@@ -505,7 +545,7 @@ def main():
                          + (", frozen model pipelined one batch ahead" if args.pipeline_teacher else "")),
             "hipgraph": bool(getattr(eng, "graph", None) is not None),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(B, H, W)
         print(json.dumps(out))
     if world > 1:

@@ -15,7 +15,7 @@ for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT TCC_MISS" "SQ_WAVE_CYCLES SQ_BUSY_CY
 done
 cd $R
 python tools/bench_kernels.py > $O/kernel_microbench.txt 2>&1
-python bench.py > $O/bench_step2.json 2> /dev/null
+python bench.py --full > $O/bench_step2.json 2> /dev/null
 # kernel-set A/B of round 5 (same box, 60 timed steps each): shipped (F(4,3) convs), F(2,3) only (round 4's conv kernels), direct form
 for r in 1 2; do
 python bench.py --steps 60 --warmup 15 --no-cpu-baseline --profile-steps 0 > $O/bench_step2_f43_$r.json 2> /dev/null
@@ -24,7 +24,7 @@ MDIL_NO_WCONV=1 python bench.py --steps 60 --warmup 15 --no-cpu-baseline --profi
 done
 MDIL_STAGGER=off python bench.py --steps 60 --warmup 15 --no-cpu-baseline --profile-steps 0 > $O/bench_step2_lockstep.json 2> /dev/null
 python bench.py --steps 60 --warmup 15 --no-cpu-baseline --profile-steps 0 --single-stream > $O/bench_step2_single_stream.json 2> /dev/null
-for w in step1 step3 multitask eval; do python bench.py --workload $w --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_$w.json 2> /dev/null; done
+for w in step1 step3 multitask eval; do python bench.py --full --workload $w --steps 30 --warmup 5 --no-cpu-baseline > $O/bench_$w.json 2> /dev/null; done
 python tools/bench_loader.py --workers 4 8 16 --cached --device > $O/loader_throughput.txt 2>&1
 python tools/host_contention.py > $O/host_contention.txt 2>&1
 ls $O
