@@ -12,32 +12,16 @@ import json
 from argparse import ArgumentParser
 
 import torch
-from torch.utils.data import DataLoader
 
-from .dataset import ProceduralSeg, add_datadir_flags, open_dataset, to_device_batch
-from .iouEval import iouEval
+from .dataset import ProceduralSeg, add_datadir_flags, open_dataset
 from .models.erfnet_RA_parallel import Net as Net_RAP
-from .train_new_task_step2 import CrossEntropyLoss2d, class_weights, _strip
-
-WEIGHT_NAME = {"cityscapes": "cityscapes", "CS": "cityscapes", "BDD": "BDD", "IDD": "IDD"}
+from .trainer_common import WEIGHT_NAME, CrossEntropyLoss2d, _strip, class_weights, make_loader, validate
 
 
 def eval(model, dataset_loader, criterion, task, num_classes):
-    model.eval()
-    dev = next(model.parameters()).device
-    num_cls = num_classes[task]
-    meter = iouEval(num_cls, num_cls - 1)
-    loss_sum, n = torch.zeros((), device=dev), 0
-    with torch.no_grad():
-        for batch in dataset_loader:
-            inputs, targets = to_device_batch(batch, dev, num_cls)
-            outputs = model(inputs, task)
-            loss_sum += criterion(outputs, targets[:, 0])
-            n += 1
-            meter.addBatch(outputs, targets)
-    iou_val, iou_classes = meter.getIoU()
-    eval.last_loss = float(loss_sum) / max(n, 1)
-    return iou_classes, float(iou_val)
+    eval.last_loss, iou_val, iou_classes = validate(model, lambda x: model(x, task), dataset_loader,
+                                                    criterion, num_classes[task], broadcast=False)
+    return iou_classes, iou_val
 
 
 def main(args):
@@ -57,7 +41,7 @@ def main(args):
                                seed=12 + task, domain=task)
         else:
             ds = open_dataset(name, "val", args, augment=False)
-        loader = DataLoader(ds, num_workers=args.num_workers, batch_size=args.batch_size)
+        loader = make_loader(ds, args, False, args.batch_size, False)
         criterion = CrossEntropyLoss2d(class_weights(WEIGHT_NAME[name]).to(dev))
         iou_classes, miou = eval(model, loader, criterion, task, args.num_classes)
         report[name] = {"task": task, "mIoU": miou, "val_loss": eval.last_loss,
