@@ -1,0 +1,171 @@
+"""What the three inference drivers (predict.py, fullres.py, ensemble.py) share: the argument checks
+of their ``*_head`` entry points -- each takes the entry point's name, so every message reads as it
+always did -- the checkpoint loader, the byte batch -> image tensor step, the bounded PNG writer and
+the score report of their command lines."""
+import json
+import os
+from argparse import ArgumentParser
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+MAX_PNG_THREADS = 16
+
+
+# ------------------------------------------------------------------------- entry-point checks
+def chk(fn, path, t, name, dtype=torch.float32):
+    """``fn``: "predict_head" ...; ``path``: what the message calls the path ("prediction" ...)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        got = (f"{t.dtype}, {t.device}, contiguous={t.is_contiguous()}" if isinstance(t, torch.Tensor)
+               else type(t).__name__)
+        raise RuntimeError(f"mdil {fn}: {name} must be a contiguous {str(dtype)[6:]} device tensor "
+                           f"(got {got}); there is no CPU fallback in the {path} path")
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def check_params(fn, w, b, x=None):
+    """The ``ConvTranspose2d(16, nc, 2, 2)`` parameters, judged together with the one feature tensor
+    ``x`` when there is one (the ensemble judges its views itself).  -> nc"""
+    bad = w.dim() != 4 or w.shape[0] != 16 or tuple(w.shape[2:]) != (2, 2) or b.numel() != w.shape[1]
+    if x is not None:
+        if x.dim() != 4 or x.shape[3] != 16 or x.numel() == 0 or bad:
+            raise RuntimeError(f"mdil {fn}: expects NHWC features [N,H,W,16] and ConvTranspose2d(16, nc, 2, 2) "
+                               f"parameters (got x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(b.shape)})")
+    elif bad:
+        raise RuntimeError(f"mdil {fn}: expects ConvTranspose2d(16, nc, 2, 2) parameters as weight and bias "
+                           f"(got w {tuple(w.shape)}, bias {tuple(b.shape)})")
+    return w.shape[1]
+
+
+def check_classes(fn, lib, nc, x, w, b, what="features"):
+    """The class range of the binding module ``lib``, then weight and bias on ``x``'s device."""
+    if not lib.MIN_CLASSES <= nc <= lib.MAX_CLASSES:
+        raise RuntimeError(f"mdil {fn}: {nc} classes (supported: {lib.MIN_CLASSES} to {lib.MAX_CLASSES})")
+    if w.device != x.device or b.device != x.device:
+        raise RuntimeError(f"mdil {fn}: {what} on {x.device}, weight on {w.device}, bias on {b.device}")
+
+
+def check_out_size(fn, lib, out_size):
+    """-> (Ho, Wo)"""
+    try:
+        Ho, Wo = (int(v) for v in out_size)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"mdil {fn}: out_size must be (height, width), got {out_size!r}") from None
+    if not (1 <= Ho <= lib.MAX_SIZE and 1 <= Wo <= lib.MAX_SIZE):
+        raise RuntimeError(f"mdil {fn}: out_size {Ho} x {Wo} outside [1, {lib.MAX_SIZE}]")
+    return Ho, Wo
+
+
+def check_tables(fn, path, dev, dtype, tables):
+    """``tables``: (tensor or None, name, shape); those given must be ``dtype`` of that shape on ``dev``."""
+    for t, name, shape in tables:
+        if t is not None:
+            chk(fn, path, t, name, dtype)
+            if tuple(t.shape) != shape or t.device != dev:
+                raise RuntimeError(f"mdil {fn}: {name} must be {str(dtype)[6:]} {list(shape)} on {dev} "
+                                   f"(got {tuple(t.shape)} on {t.device})")
+
+
+def check_scoring(fn, path, dev, N, nc, Ho, Wo, id_map, palette, target, confusion, bad_targets, ignore_index):
+    check_tables(fn, path, dev, torch.uint8,
+                 ((id_map, "id_map", (nc,)), (palette, "palette", (nc, 3)), (target, "target", (N, Ho, Wo))))
+    if target is None:
+        if confusion is not None or bad_targets is not None:
+            raise RuntimeError(f"mdil {fn}: confusion / bad_targets given without a target")
+    else:
+        if confusion is None or bad_targets is None:
+            raise RuntimeError(f"mdil {fn}: a target needs confusion (int64 [nc,nc]) and bad_targets "
+                               "(int64 [1]) on the device; they are accumulated into")
+        check_tables(fn, path, dev, torch.int64,
+                     ((confusion, "confusion", (nc, nc)), (bad_targets, "bad_targets", (1,))))
+    if not -1 <= int(ignore_index) <= 255:
+        raise RuntimeError(f"mdil {fn}: ignore_index {ignore_index} outside [-1, 255]")
+
+
+# -------------------------------------------------------------------------------- command lines
+class RefusingParser(ArgumentParser):
+    """An ArgumentParser whose ``parse_args`` also runs ``refusals(args)`` and reports its
+    RuntimeError as a usage error."""
+
+    def __init__(self, refusals, **kw):
+        super().__init__(**kw)
+        self.refusals = refusals
+
+    def parse_args(self, *a, **kw):
+        args = super().parse_args(*a, **kw)
+        try:
+            self.refusals(args)
+        except RuntimeError as e:
+            self.error(str(e))
+        return args
+
+
+def load_model(args):
+    """-> (device, class count of ``args.task``, Net_RAP with ``args.state`` loaded, in eval mode)."""
+    from .models.erfnet_RA_parallel import Net as Net_RAP
+    from .trainer_common import _strip
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    nb = len(args.num_classes)
+    if not 0 <= args.task < nb:
+        raise RuntimeError(f"--task {args.task}: the model has tasks 0 to {nb - 1}")
+    model = Net_RAP(args.num_classes, nb, nb - 1)
+    saved = torch.load(args.state, map_location="cpu", weights_only=False)
+    model.load_state_dict(_strip(saved["state_dict"]), strict=True)
+    model.to(dev).eval()
+    return dev, args.num_classes[args.task], model
+
+
+def image_batch(arrays, dev):
+    """uint8 [h,w,3] arrays -> f32 [n,3,h,w] in [0, 1] on the device (the bytes cross the bus)."""
+    u8 = torch.from_numpy(np.stack(arrays)).to(dev)
+    return u8.permute(0, 3, 1, 2).to(torch.float32).div_(255.0)
+
+
+def _save_png(arr, path):
+    from PIL import Image
+    Image.fromarray(arr).save(path)
+
+
+def png_pool():
+    return ThreadPoolExecutor(max_workers=min(MAX_PNG_THREADS, os.cpu_count() or 1))
+
+
+class PngWriter:
+    """Writes maps on ``pool`` with a bound on what is in flight: ``wait()`` before submitting a
+    batch, so that at most the batch before it is still being written.  ``written``: every path."""
+
+    def __init__(self, pool, out):
+        self.pool, self.out, self.written, self.pending = pool, out, [], []
+
+    def wait(self):
+        for f in self.pending:
+            f.result()
+        self.pending = []
+
+    def submit(self, arr, name):
+        path = os.path.join(self.out, name)
+        self.pending.append(self.pool.submit(_save_png, np.ascontiguousarray(arr), path))
+        self.written.append(path)
+
+
+def score_report(report, meter, args, how=""):
+    """Adds the meter's score to ``report`` and prints it; then the maps line and the JSON file."""
+    if meter is not None:
+        matrix = meter.matrix()
+        miou, per_class = meter.iou(matrix)
+        report.update(mIoU=float(miou), iou_classes=[float(v) for v in per_class], confusion=matrix.tolist(),
+                      pixels=int(matrix.sum()))
+        print(f"{report['dataset']} (task {args.task}) at the labels' own size{how}: "
+              f"mIoU {float(miou) * 100:.2f} %  over {report['pixels']} pixels")
+        print("per-class IoU: " + " ".join(f"{float(v) * 100:.2f}" for v in per_class))
+    if args.out:
+        print(f"{len(report['written'])} maps written to {args.out}")
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(report, f, indent=1)
+    return report

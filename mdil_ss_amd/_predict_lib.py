@@ -4,6 +4,8 @@ RuntimeError is raised."""
 import ctypes as C
 import os
 
+from . import _addon_lib
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmdil_predict.so")
 MIN_CLASSES, MAX_CLASSES = 2, 32              # MDIL_PREDICT_MIN_CLASSES / _MAX_CLASSES
@@ -18,29 +20,4 @@ _SIGNATURES = {
 }
 
 EXPORTS = tuple(_SIGNATURES)
-_lib = None
-
-
-def load():
-    """Load (once) and return the ctypes handle; raises RuntimeError when the library is absent."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            f"libmdil_predict.so not found at {LIB_PATH}: build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
-            "There is no CPU / eager fallback for the prediction path.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
-
-
-def check(rc, what):
-    if rc != 0:
-        msg = load().mdil_predict_last_error().decode()
-        raise RuntimeError(f"{what} failed (rc={rc}): {msg}")
+load, check = _addon_lib.bind(LIB_PATH, _SIGNATURES, "mdil_predict", "prediction")

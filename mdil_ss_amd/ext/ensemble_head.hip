@@ -64,17 +64,8 @@
 //
 // Confusion.  As in fullres_head.hip: a [nc][nc] histogram of 32-bit counters in LDS (LDS atomics),
 // added to the 64-bit matrix with global atomic adds after the loop (and every 2^20 trips).
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-
 #include "../../include/mdil_ensemble.h"
-
-#define API extern "C" __attribute__((visibility("default")))
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "head_common.h"
 
 namespace {
 
@@ -82,8 +73,9 @@ constexpr int kWG = 64;                              // one wavefront
 constexpr int kMaxC = MDIL_ENSEMBLE_MAX_CLASSES;
 constexpr int kMaxV = MDIL_ENSEMBLE_MAX_VIEWS;
 constexpr int kMaxBlocks = 8192;                     // beyond 524,288 items (of 2 pixels) the loop strides
-constexpr int kFlushEvery = 1 << 20;                 // trips; a trip adds at most 128 counts per work-group
 constexpr float kLog2e = 1.44269504088896340736f;
+constexpr int kFlushEvery = 1 << 20;                 // trips; a trip adds at most 128 counts per work-group
+constexpr char kFn[] = "ensemble_head";
 
 struct ViewTable {
   const float* x[kMaxV];
@@ -91,76 +83,6 @@ struct ViewTable {
   int W[kMaxV];
   int mirrored[kMaxV];
 };
-
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-// One axis of the resize: output index o of O, source length L (even, >= 2).  -> first source
-// index i0, its weight w0 and the weight w1 of i0 + 1 (0 where i0 + 1 would be clamped).
-__device__ __forceinline__ void axis(int o, int L, int O, int& i0, float& w0, float& w1) {
-  const long long num = (2LL * o + 1) * L - O;
-  const int den = 2 * O;
-  int rem = 0;
-  i0 = 0;
-  if (num > 0) {
-    i0 = (int)(num / den);
-    rem = (int)(num - (long long)i0 * den);
-  }
-  if (i0 >= L - 1) {
-    i0 = L - 1;
-    rem = 0;
-  }
-  w1 = (float)rem / (float)den;
-  w0 = (float)(den - rem) / (float)den;
-}
-
-// The four neighbours of one output pixel, scaled: s[ci][a*2+b'] = wt[a][b'] * x[ci].
-// rowoff[a]: (n*H + h) * W of the feature row under the logit row of parity a; wy[a] its weight.
-// Columns are those of l' (the view's own grid); a mirrored view reads feature column W - 1 - col.
-__device__ __forceinline__ void gather(const float* __restrict__ x, const long long (&rowoff)[2],
-                                       const float (&wy)[2], int xo, int Wl, int Wo, int W, bool mir,
-                                       f32x4 (&s)[16]) {
-  int x0;
-  float wx0, wx1;
-  axis(xo, Wl, Wo, x0, wx0, wx1);
-  const bool odd = x0 & 1;
-  int c0 = x0 >> 1;                                          // feature column under x0
-  int c1 = min((x0 + 1) >> 1, W - 1);                        // ... under x0 + 1 (weight 0 when clamped)
-  if (mir) {
-    c0 = W - 1 - c0;
-    c1 = W - 1 - c1;
-  }
-  const int col[2] = {odd ? c1 : c0, odd ? c0 : c1};         // by parity b'
-  const float wx[2] = {odd ? wx1 : wx0, odd ? wx0 : wx1};
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const float wt = wy[a] * wx[b];
-      const float* p = x + (rowoff[a] + col[b]) * 16;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p + j * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[j * 4 + e][a * 2 + b] = wt * v[e];
-      }
-    }
-  }
-}
-
-// strictly greater keeps the lowest index of a tie; a NaN replaces any number and is never
-// replaced (both comparisons are false against a NaN `best`); class 0 always enters
-__device__ __forceinline__ void vote(int c, float u, float& best, int& bi) {
-  const bool t = c == 0 || u > best || (u != u && best == best);
-  best = t ? u : best;
-  bi = t ? c : bi;
-}
 
 template <bool PROB>
 __global__ __launch_bounds__(kWG) void ensemble_head_kernel(
@@ -181,7 +103,7 @@ __global__ __launch_bounds__(kWG) void ensemble_head_kernel(
   float* const Tm = dyn + nc * 64;
   f32x2* const Sl = reinterpret_cast<f32x2*>(dyn + nc * 128) + threadIdx.x;          // [c * kWG]
   f32x2* const El = Sl + nc * kWG;                                                   // PROB only
-  for (int i = threadIdx.x; i < nc * 64; i += kWG) {
+  for (int i = threadIdx.x; i < nc * 64; i += kWG) {     // head_common.h's stage_head, for two flat tables
     const int k = i & 3, ci = (i >> 2) & 15, c = i >> 6;
     Tp[i] = w[(ci * nc + c) * 4 + k];
     Tm[i] = w[(ci * nc + c) * 4 + (k ^ 1)];
@@ -193,8 +115,7 @@ __global__ __launch_bounds__(kWG) void ensemble_head_kernel(
                    : 0u;
     Il[c] = id_map ? (uint32_t)id_map[c] : (uint32_t)c;
   }
-  for (int i = threadIdx.x; i < nc * nc; i += kWG) hist[i] = 0u;
-  if (threadIdx.x == 0) bad = 0u;
+  confusion_zero<kWG>(hist, bad, nc);
   __syncthreads();
 
   const long long G = ((long long)Wo + 1) >> 1;          // items per output row
@@ -371,19 +292,12 @@ API int mdil_ensemble_head(const mdil_ensemble_view* views, int nviews, const fl
               (const void*)views, (const void*)w, (const void*)bias, (void*)label, N, Ho, Wo);
     return MDIL_ENSEMBLE_ERR_INVALID;
   }
-  if (nc < MDIL_ENSEMBLE_MIN_CLASSES || nc > MDIL_ENSEMBLE_MAX_CLASSES) {
-    set_error("ensemble_head: nc=%d outside [%d, %d]", nc, MDIL_ENSEMBLE_MIN_CLASSES,
-              MDIL_ENSEMBLE_MAX_CLASSES);
-    return MDIL_ENSEMBLE_ERR_INVALID;
-  }
+  if (!classes_ok(kFn, nc, MDIL_ENSEMBLE_MIN_CLASSES, MDIL_ENSEMBLE_MAX_CLASSES)) return MDIL_ENSEMBLE_ERR_INVALID;
   if (mode != MDIL_ENSEMBLE_MODE_PROB && mode != MDIL_ENSEMBLE_MODE_LOGIT) {
     set_error("ensemble_head: mode=%d is neither MDIL_ENSEMBLE_MODE_PROB (0) nor _LOGIT (1)", mode);
     return MDIL_ENSEMBLE_ERR_INVALID;
   }
-  if (Ho > MDIL_ENSEMBLE_MAX_SIZE || Wo > MDIL_ENSEMBLE_MAX_SIZE) {
-    set_error("ensemble_head: output size %d x %d above %d", Ho, Wo, MDIL_ENSEMBLE_MAX_SIZE);
-    return MDIL_ENSEMBLE_ERR_INVALID;
-  }
+  if (!out_size_ok(kFn, Ho, Wo, MDIL_ENSEMBLE_MAX_SIZE)) return MDIL_ENSEMBLE_ERR_INVALID;
   if ((long long)N * Ho > MDIL_ENSEMBLE_MAX_PIXELS / Wo) {
     set_error("ensemble_head: too large (N %d, output %d x %d: at most 2^40 pixels)", N, Ho, Wo);
     return MDIL_ENSEMBLE_ERR_INVALID;
@@ -409,18 +323,8 @@ API int mdil_ensemble_head(const mdil_ensemble_view* views, int nviews, const fl
     table.W[v] = V.W;
     table.mirrored[v] = V.mirrored != 0;
   }
-  if (colour && !palette) {
-    set_error("ensemble_head: a colour map needs a palette");
+  if (!colour_ok(kFn, colour, palette) || !scoring_ok(kFn, target, confusion, bad_targets, ignore_index))
     return MDIL_ENSEMBLE_ERR_INVALID;
-  }
-  if (target && (!confusion || !bad_targets)) {
-    set_error("ensemble_head: a target needs a confusion matrix and a bad_targets counter");
-    return MDIL_ENSEMBLE_ERR_INVALID;
-  }
-  if (ignore_index < -1 || ignore_index > 255) {
-    set_error("ensemble_head: ignore_index=%d outside [-1, 255]", ignore_index);
-    return MDIL_ENSEMBLE_ERR_INVALID;
-  }
   if (((uintptr_t)label & 3) || ((uintptr_t)colour & 3) || ((uintptr_t)target & 3) ||
       ((uintptr_t)confidence & 3) || ((uintptr_t)confusion & 7) || ((uintptr_t)bad_targets & 7)) {
     set_error("ensemble_head: alignment (label, colour, target and confidence 4 B; confusion and bad_targets 8 B)");
@@ -428,8 +332,7 @@ API int mdil_ensemble_head(const mdil_ensemble_view* views, int nviews, const fl
   }
   const bool prob = mode == MDIL_ENSEMBLE_MODE_PROB;
   const long long nitems = (long long)N * Ho * (((long long)Wo + 1) >> 1);
-  const long long blocks = (nitems + kWG - 1) / kWG;
-  const int grid = (int)(blocks > kMaxBlocks ? kMaxBlocks : blocks);
+  const int grid = bounded_grid(nitems, kWG, kMaxBlocks);
   // two weight tables of nc * 64 floats, then nc * 64 float2 once (S) or twice (S and E): at most 48 KB
   const size_t lds = (size_t)nc * 64 * sizeof(float) * (2 + (prob ? 4 : 2));
   auto* cf = reinterpret_cast<unsigned long long*>(confusion);
@@ -442,10 +345,5 @@ API int mdil_ensemble_head(const mdil_ensemble_view* views, int nviews, const fl
     hipLaunchKernelGGL(ensemble_head_kernel<false>, dim3(grid), dim3(kWG), lds, (hipStream_t)stream, table,
                        nviews, w, bias, nitems, nc, Ho, Wo, id_map, palette, target, ignore_index, label,
                        colour, confidence, cf, bt);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("ensemble_head: launch failed: %s", hipGetErrorString(e));
-    return MDIL_ENSEMBLE_ERR_LAUNCH;
-  }
-  return MDIL_ENSEMBLE_OK;
+  return launched(kFn) ? MDIL_ENSEMBLE_OK : MDIL_ENSEMBLE_ERR_LAUNCH;
 }

@@ -42,16 +42,8 @@
 // atomics) and adds its non-zero entries to the 64-bit matrix with global atomic adds after its
 // loop (and every 2^20 trips, before a counter could wrap).  Every item is visited by exactly one
 // lane once, so every pixel is counted once whatever the grid is.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-
 #include "../../include/mdil_fullres.h"
-
-#define API extern "C" __attribute__((visibility("default")))
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "head_common.h"
 
 namespace {
 
@@ -59,63 +51,7 @@ constexpr int kWG = 256;                             // 4 wavefronts of 64 lanes
 constexpr int kMaxC = MDIL_FULLRES_MAX_CLASSES;
 constexpr int kMaxBlocks = 2048;                     // beyond 524,288 items (of 4 pixels) the loop strides
 constexpr int kFlushEvery = 1 << 20;                 // trips; a trip adds at most 1024 counts per work-group
-
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-// One axis of the resize: output index o of O, source length L (even, >= 2).  -> first source
-// index i0, its weight w0 and the weight w1 of i0 + 1 (0 where i0 + 1 would be clamped).
-__device__ __forceinline__ void axis(int o, int L, int O, int& i0, float& w0, float& w1) {
-  const long long num = (2LL * o + 1) * L - O;
-  const int den = 2 * O;
-  int rem = 0;
-  i0 = 0;
-  if (num > 0) {
-    i0 = (int)(num / den);
-    rem = (int)(num - (long long)i0 * den);
-  }
-  if (i0 >= L - 1) {
-    i0 = L - 1;
-    rem = 0;
-  }
-  w1 = (float)rem / (float)den;
-  w0 = (float)(den - rem) / (float)den;
-}
-
-// The four neighbours of one output pixel, scaled: s[ci][a*2+b] = wt[a][b] * x_ab[ci].
-// rowoff[a]: (n*H + h) * W of the feature row under the logit row of parity a; wy[a] its weight.
-__device__ __forceinline__ void gather(const float* __restrict__ x, const long long (&rowoff)[2],
-                                       const float (&wy)[2], int xo, int Wl, int Wo, int W,
-                                       f32x4 (&s)[16]) {
-  int x0;
-  float wx0, wx1;
-  axis(xo, Wl, Wo, x0, wx0, wx1);
-  const bool odd = x0 & 1;
-  const int c0 = x0 >> 1;                                    // feature column under x0
-  const int c1 = min((x0 + 1) >> 1, W - 1);                  // ... under x0 + 1 (weight 0 when clamped)
-  const int col[2] = {odd ? c1 : c0, odd ? c0 : c1};         // by parity b
-  const float wx[2] = {odd ? wx1 : wx0, odd ? wx0 : wx1};
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const float wt = wy[a] * wx[b];
-      const float* p = x + (rowoff[a] + col[b]) * 16;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p + j * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[j * 4 + e][a * 2 + b] = wt * v[e];
-      }
-    }
-  }
-}
+constexpr char kFn[] = "fullres_head";
 
 __global__ __launch_bounds__(kWG, 2) void fullres_head_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
@@ -130,19 +66,8 @@ __global__ __launch_bounds__(kWG, 2) void fullres_head_kernel(
   __shared__ uint32_t Il[kMaxC];                                     // byte written for class c
   __shared__ uint32_t hist[kMaxC * kMaxC];                           // [target][prediction]
   __shared__ uint32_t bad;
-  for (int i = threadIdx.x; i < nc * 64; i += kWG) {
-    const int k = i & 3, ci = (i >> 2) & 15, c = i >> 6;
-    Wl[c][ci][k] = w[(ci * nc + c) * 4 + k];
-  }
-  for (int c = threadIdx.x; c < nc; c += kWG) {
-    Bl[c] = bias[c];
-    Pl[c] = colour ? (uint32_t)palette[3 * c] | (uint32_t)palette[3 * c + 1] << 8 |
-                         (uint32_t)palette[3 * c + 2] << 16
-                   : 0u;
-    Il[c] = id_map ? (uint32_t)id_map[c] : (uint32_t)c;
-  }
-  for (int i = threadIdx.x; i < nc * nc; i += kWG) hist[i] = 0u;
-  if (threadIdx.x == 0) bad = 0u;
+  stage_head<kWG, true>(w, bias, palette, colour, id_map, nc, Wl, Bl, Pl, Il);
+  confusion_zero<kWG>(hist, bad, nc);
   __syncthreads();
 
   const int Hl = 2 * H, Wlog = 2 * W;
@@ -173,9 +98,9 @@ __global__ __launch_bounds__(kWG, 2) void fullres_head_kernel(
       for (int half = 0; half < 2; ++half) {
         f32x4 s0[16], s1[16];
         const int xa = min(4 * g + 2 * half, Wo - 1), xb = min(4 * g + 2 * half + 1, Wo - 1);
-        gather(x, rowoff, wy, xa, Wlog, Wo, W, s0);
+        gather(x, rowoff, wy, xa, Wlog, Wo, W, false, s0);
         __builtin_amdgcn_sched_barrier(0);                 // one pixel's 16 loads in flight at a time
-        gather(x, rowoff, wy, xb, Wlog, Wo, W, s1);
+        gather(x, rowoff, wy, xb, Wlog, Wo, W, false, s1);
         __builtin_amdgcn_sched_barrier(0);
         float best0 = 0.f, best1 = 0.f;
         int bi0 = 0, bi1 = 0;
@@ -190,8 +115,9 @@ __global__ __launch_bounds__(kWG, 2) void fullres_head_kernel(
               u1 = __builtin_fmaf(s1[ci][k], wv[k], u1);
             }
           }
-          // strictly greater keeps the lowest index of a tie; a NaN replaces any number and is
-          // never replaced (both comparisons are false against a NaN `best`); class 0 always enters
+          // head_common.h's vote, spelled out: calling it changes this kernel's register allocation
+          // (254 -> 222 VGPRs) and instruction mix.  Strictly greater keeps the lowest index of a
+          // tie; a NaN replaces any number and is never replaced; class 0 always enters
           const bool t0 = c == 0 || u0 > best0 || (u0 != u0 && best0 == best0);
           const bool t1 = c == 0 || u1 > best1 || (u1 != u1 && best1 == best1);
           best0 = t0 ? u0 : best0;
@@ -288,49 +214,27 @@ API int mdil_fullres_head(const float* x, const float* w, const float* bias, int
               (const void*)x, (const void*)w, (const void*)bias, (void*)label, N, H, W, Ho, Wo);
     return MDIL_FULLRES_ERR_INVALID;
   }
-  if (nc < MDIL_FULLRES_MIN_CLASSES || nc > MDIL_FULLRES_MAX_CLASSES) {
-    set_error("fullres_head: nc=%d outside [%d, %d]", nc, MDIL_FULLRES_MIN_CLASSES,
-              MDIL_FULLRES_MAX_CLASSES);
+  if (!classes_ok(kFn, nc, MDIL_FULLRES_MIN_CLASSES, MDIL_FULLRES_MAX_CLASSES) ||
+      !out_size_ok(kFn, Ho, Wo, MDIL_FULLRES_MAX_SIZE))
     return MDIL_FULLRES_ERR_INVALID;
-  }
-  if (Ho > MDIL_FULLRES_MAX_SIZE || Wo > MDIL_FULLRES_MAX_SIZE) {
-    set_error("fullres_head: output size %d x %d above %d", Ho, Wo, MDIL_FULLRES_MAX_SIZE);
-    return MDIL_FULLRES_ERR_INVALID;
-  }
   if (H > (1 << 29) || W > (1 << 29) || (long long)N * H > MDIL_FULLRES_MAX_PIXELS / W ||
       (long long)N * Ho > MDIL_FULLRES_MAX_PIXELS / Wo) {
     set_error("fullres_head: too large (N %d, features %d x %d, output %d x %d: at most 2^40 pixels)",
               N, H, W, Ho, Wo);
     return MDIL_FULLRES_ERR_INVALID;
   }
-  if (colour && !palette) {
-    set_error("fullres_head: a colour map needs a palette");
+  if (!colour_ok(kFn, colour, palette) || !scoring_ok(kFn, target, confusion, bad_targets, ignore_index))
     return MDIL_FULLRES_ERR_INVALID;
-  }
-  if (target && (!confusion || !bad_targets)) {
-    set_error("fullres_head: a target needs a confusion matrix and a bad_targets counter");
-    return MDIL_FULLRES_ERR_INVALID;
-  }
-  if (ignore_index < -1 || ignore_index > 255) {
-    set_error("fullres_head: ignore_index=%d outside [-1, 255]", ignore_index);
-    return MDIL_FULLRES_ERR_INVALID;
-  }
   if (((uintptr_t)x & 15) || ((uintptr_t)label & 3) || ((uintptr_t)colour & 3) ||
       ((uintptr_t)target & 3) || ((uintptr_t)confusion & 7) || ((uintptr_t)bad_targets & 7)) {
     set_error("fullres_head: alignment (x 16 B; label, colour and target 4 B; confusion and bad_targets 8 B)");
     return MDIL_FULLRES_ERR_INVALID;
   }
   const long long nitems = (long long)N * Ho * (((long long)Wo + 3) >> 2);
-  const long long blocks = (nitems + kWG - 1) / kWG;
-  const int grid = (int)(blocks > kMaxBlocks ? kMaxBlocks : blocks);
+  const int grid = bounded_grid(nitems, kWG, kMaxBlocks);
   hipLaunchKernelGGL(fullres_head_kernel, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, x, w, bias,
                      nitems, H, W, nc, Ho, Wo, id_map, palette, target, ignore_index, label, colour,
                      reinterpret_cast<unsigned long long*>(confusion),
                      reinterpret_cast<unsigned long long*>(bad_targets));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("fullres_head: launch failed: %s", hipGetErrorString(e));
-    return MDIL_FULLRES_ERR_LAUNCH;
-  }
-  return MDIL_FULLRES_OK;
+  return launched(kFn) ? MDIL_FULLRES_OK : MDIL_FULLRES_ERR_LAUNCH;
 }

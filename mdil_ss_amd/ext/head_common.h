@@ -1,0 +1,171 @@
+// What predict_head.hip, fullres_head.hip and ensemble_head.hip share, written once.  Private to
+// mdil_ss_amd/ext (not under include/): it is compiled INTO each of the three libraries, which stay
+// self-contained binaries -- the error buffer below is one per library -- and it shares nothing
+// with csrc/.  The arithmetic contracts (order of operations, roundings) are documented in the
+// three kernels' header comments; the helpers here are the single spelling of the steps they name.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#define API extern "C" __attribute__((visibility("default")))
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+namespace {
+
+thread_local char g_err[512] = "";
+
+__attribute__((format(printf, 1, 2))) void set_error(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+}
+
+// ------------------------------------------------------------------------------------ device
+// One axis of the resize: output index o of O, source length L (even, >= 2).  -> first source
+// index i0, its weight w0 and the weight w1 of i0 + 1 (0 where i0 + 1 would be clamped).
+__device__ __forceinline__ void axis(int o, int L, int O, int& i0, float& w0, float& w1) {
+  const long long num = (2LL * o + 1) * L - O;
+  const int den = 2 * O;
+  int rem = 0;
+  i0 = 0;
+  if (num > 0) {
+    i0 = (int)(num / den);
+    rem = (int)(num - (long long)i0 * den);
+  }
+  if (i0 >= L - 1) {
+    i0 = L - 1;
+    rem = 0;
+  }
+  w1 = (float)rem / (float)den;
+  w0 = (float)(den - rem) / (float)den;
+}
+
+// The four neighbours of one output pixel, scaled: s[ci][a*2+b'] = wt[a][b'] * x[ci].
+// rowoff[a]: (n*H + h) * W of the feature row under the logit row of parity a; wy[a] its weight.
+// Columns are those of l' (the view's own grid); a mirrored view reads feature column W - 1 - col.
+__device__ __forceinline__ void gather(const float* __restrict__ x, const long long (&rowoff)[2],
+                                       const float (&wy)[2], int xo, int Wl, int Wo, int W, bool mir,
+                                       f32x4 (&s)[16]) {
+  int x0;
+  float wx0, wx1;
+  axis(xo, Wl, Wo, x0, wx0, wx1);
+  const bool odd = x0 & 1;
+  int c0 = x0 >> 1;                                          // feature column under x0
+  int c1 = min((x0 + 1) >> 1, W - 1);                        // ... under x0 + 1 (weight 0 when clamped)
+  if (mir) {
+    c0 = W - 1 - c0;
+    c1 = W - 1 - c1;
+  }
+  const int col[2] = {odd ? c1 : c0, odd ? c0 : c1};         // by parity b'
+  const float wx[2] = {odd ? wx1 : wx0, odd ? wx0 : wx1};
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const float wt = wy[a] * wx[b];
+      const float* p = x + (rowoff[a] + col[b]) * 16;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(p + j * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[j * 4 + e][a * 2 + b] = wt * v[e];
+      }
+    }
+  }
+}
+
+// The argmax step.  Strictly greater keeps the lowest index of a tie; a NaN replaces any number
+// and is never replaced (both comparisons are false against a NaN `best`); class 0 always enters.
+__device__ __forceinline__ void vote(int c, float u, float& best, int& bi) {
+  const bool t = c == 0 || u > best || (u != u && best == best);
+  best = t ? u : best;
+  bi = t ? c : bi;
+}
+
+// Stages the head's tables into LDS, by a work-group of WG lanes (the caller's barrier follows):
+//   Wl[c][ci][a*2+b] = W[ci][c][a][b];  Bl[c] = bias[c];
+//   Pl[c] = r | g << 8 | b << 16 of the palette (0 without a `colour` map);
+//   IDS: Il[c], the byte written for class c (id_map, default c).
+// ensemble_head.hip keeps its own staging: its two tables (plain and column-swapped) are flat
+// arrays in dynamic LDS, and going through this routine changes its address arithmetic.
+template <int WG, bool IDS>
+__device__ __forceinline__ void stage_head(const float* w, const float* bias, const unsigned char* palette,
+                                           const void* colour, const unsigned char* id_map, int nc,
+                                           float (*Wl)[16][4], float* Bl, uint32_t* Pl, uint32_t* Il) {
+  for (int i = threadIdx.x; i < nc * 64; i += WG) {
+    const int k = i & 3, ci = (i >> 2) & 15, c = i >> 6;
+    Wl[c][ci][k] = w[(ci * nc + c) * 4 + k];
+  }
+  for (int c = threadIdx.x; c < nc; c += WG) {
+    Bl[c] = bias[c];
+    Pl[c] = colour ? (uint32_t)palette[3 * c] | (uint32_t)palette[3 * c + 1] << 8 |
+                         (uint32_t)palette[3 * c + 2] << 16
+                   : 0u;
+    if (IDS) Il[c] = id_map ? (uint32_t)id_map[c] : (uint32_t)c;
+  }
+}
+
+// Confusion: zeroes the [nc][nc] histogram of 32-bit counters (row = target) and the counter of
+// targets >= nc in LDS.  Counting a (target, prediction) pair and the work-group-uniform flush
+// into the 64-bit matrix stay spelled out in fullres_head.hip and ensemble_head.hip: as inlined
+// helpers they compile to different code in both kernels (a select instead of a branch, another
+// block order), and the kernels' code is not to move.
+template <int WG, int N>
+__device__ __forceinline__ void confusion_zero(uint32_t (&hist)[N], uint32_t& bad, int nc) {
+  for (int i = threadIdx.x; i < nc * nc; i += WG) hist[i] = 0u;
+  if (threadIdx.x == 0) bad = 0u;
+}
+
+// -------------------------------------------------------------------------------------- host
+// Work-groups of `wg` lanes for `items`, at most `max_blocks`: beyond that the kernels' loops stride.
+inline int bounded_grid(long long items, int wg, int max_blocks) {
+  const long long blocks = (items + wg - 1) / wg;
+  return (int)(blocks > max_blocks ? max_blocks : blocks);
+}
+
+// After hipLaunchKernelGGL: true when the launch was accepted.
+inline bool launched(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return true;
+  set_error("%s: launch failed: %s", fn, hipGetErrorString(e));
+  return false;
+}
+
+// The argument checks: each sets the entry point's message and returns false on a refusal.
+inline bool classes_ok(const char* fn, int nc, int lo, int hi) {
+  if (nc >= lo && nc <= hi) return true;
+  set_error("%s: nc=%d outside [%d, %d]", fn, nc, lo, hi);
+  return false;
+}
+
+inline bool out_size_ok(const char* fn, int Ho, int Wo, int max_size) {
+  if (Ho <= max_size && Wo <= max_size) return true;
+  set_error("%s: output size %d x %d above %d", fn, Ho, Wo, max_size);
+  return false;
+}
+
+inline bool colour_ok(const char* fn, const void* colour, const void* palette) {
+  if (!colour || palette) return true;
+  set_error("%s: a colour map needs a palette", fn);
+  return false;
+}
+
+inline bool scoring_ok(const char* fn, const void* target, const void* confusion, const void* bad_targets,
+                       int ignore_index) {
+  if (target && (!confusion || !bad_targets)) {
+    set_error("%s: a target needs a confusion matrix and a bad_targets counter", fn);
+    return false;
+  }
+  if (ignore_index < -1 || ignore_index > 255) {
+    set_error("%s: ignore_index=%d outside [-1, 255]", fn, ignore_index);
+    return false;
+  }
+  return true;
+}
+
+}  // namespace

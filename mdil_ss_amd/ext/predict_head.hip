@@ -18,31 +18,15 @@
 // out.  Stores: a thread writes the two adjacent pixels 2w, 2w+1 of output rows 2h and 2h+1 as one
 // packed store per row and map (2 B label, 6 B colour, 8 B confidence); consecutive lanes continue
 // the row.  Grid-stride loop over feature pixels with 64-bit indices, bounded grid, any N*H*W.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-
 #include "../../include/mdil_predict.h"
-
-#define API extern "C" __attribute__((visibility("default")))
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "head_common.h"
 
 namespace {
 
 constexpr int kWG = 256;                             // 4 wavefronts of 64 lanes
 constexpr int kMaxC = MDIL_PREDICT_MAX_CLASSES;
 constexpr int kMaxBlocks = 2048;                     // beyond 524,288 feature pixels the loop strides
-
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
+constexpr char kFn[] = "predict_head";
 
 // the four logits (a*2+b) of class c for one feature pixel: bias first, then ci ascending
 __device__ __forceinline__ f32x4 logits4(const f32x4 (&xv)[4], const float (*Wc)[4], float b) {
@@ -65,16 +49,7 @@ __global__ __launch_bounds__(kWG) void predict_head_kernel(
   __shared__ __attribute__((aligned(16))) float Wl[kMaxC][16][4];   // [c][ci][a*2+b]
   __shared__ float Bl[kMaxC];
   __shared__ uint32_t Pl[kMaxC];                                     // r | g << 8 | b << 16
-  for (int i = threadIdx.x; i < nc * 64; i += kWG) {
-    const int k = i & 3, ci = (i >> 2) & 15, c = i >> 6;
-    Wl[c][ci][k] = w[(ci * nc + c) * 4 + k];
-  }
-  for (int c = threadIdx.x; c < nc; c += kWG) {
-    Bl[c] = bias[c];
-    Pl[c] = colour ? (uint32_t)palette[3 * c] | (uint32_t)palette[3 * c + 1] << 8 |
-                         (uint32_t)palette[3 * c + 2] << 16
-                   : 0u;
-  }
+  stage_head<kWG, false>(w, bias, palette, colour, nullptr, nc, Wl, Bl, Pl, nullptr);
   __syncthreads();
 
   for (long long q = (long long)blockIdx.x * kWG + threadIdx.x; q < npix;
@@ -83,18 +58,13 @@ __global__ __launch_bounds__(kWG) void predict_head_kernel(
 #pragma unroll
     for (int k = 0; k < 4; ++k) xv[k] = *reinterpret_cast<const f32x4*>(x + q * 16 + k * 4);
 
-    f32x4 best = logits4(xv, Wl[0], Bl[0]);
+    const f32x4 l0 = logits4(xv, Wl[0], Bl[0]);
+    float best[4] = {l0[0], l0[1], l0[2], l0[3]};
     int bi[4] = {0, 0, 0, 0};
     for (int c = 1; c < nc; ++c) {
       const f32x4 l = logits4(xv, Wl[c], Bl[c]);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        // strictly greater keeps the lowest index of a tie; a NaN replaces any number and is
-        // never replaced (both comparisons are false against a NaN `best`)
-        const bool take = l[k] > best[k] || (l[k] != l[k] && best[k] == best[k]);
-        best[k] = take ? l[k] : best[k];
-        bi[k] = take ? c : bi[k];
-      }
+      for (int k = 0; k < 4; ++k) vote(c, l[k], best[k], bi[k]);   // c >= 1: class 0 entered above
     }
 
     const long long r = q / W;                                   // n * H + h
@@ -144,15 +114,9 @@ API int mdil_predict_head(const float* x, const float* w, const float* bias, int
               (const void*)w, (const void*)bias, (void*)label, N, H, W);
     return MDIL_PREDICT_ERR_INVALID;
   }
-  if (nc < MDIL_PREDICT_MIN_CLASSES || nc > MDIL_PREDICT_MAX_CLASSES) {
-    set_error("predict_head: nc=%d outside [%d, %d]", nc, MDIL_PREDICT_MIN_CLASSES,
-              MDIL_PREDICT_MAX_CLASSES);
+  if (!classes_ok(kFn, nc, MDIL_PREDICT_MIN_CLASSES, MDIL_PREDICT_MAX_CLASSES) ||
+      !colour_ok(kFn, colour, palette))
     return MDIL_PREDICT_ERR_INVALID;
-  }
-  if (colour && !palette) {
-    set_error("predict_head: a colour map needs a palette");
-    return MDIL_PREDICT_ERR_INVALID;
-  }
   if (((uintptr_t)x & 15) || ((uintptr_t)label & 1) || ((uintptr_t)colour & 1) ||
       ((uintptr_t)confidence & 7)) {
     set_error("predict_head: alignment (x 16 B, label and colour 2 B, confidence 8 B)");
@@ -163,14 +127,8 @@ API int mdil_predict_head(const float* x, const float* w, const float* bias, int
     return MDIL_PREDICT_ERR_INVALID;
   }
   const long long npix = (long long)N * H * W;
-  const long long blocks = (npix + kWG - 1) / kWG;
-  const int grid = (int)(blocks > kMaxBlocks ? kMaxBlocks : blocks);
+  const int grid = bounded_grid(npix, kWG, kMaxBlocks);
   hipLaunchKernelGGL(predict_head_kernel, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, x, w, bias,
                      npix, W, nc, palette, label, colour, confidence);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("predict_head: launch failed: %s", hipGetErrorString(e));
-    return MDIL_PREDICT_ERR_LAUNCH;
-  }
-  return MDIL_PREDICT_OK;
+  return launched(kFn) ? MDIL_PREDICT_OK : MDIL_PREDICT_ERR_LAUNCH;
 }

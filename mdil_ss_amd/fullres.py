@@ -14,16 +14,16 @@ reports mIoU and per-class IoU by the reference's ``iouEval`` rule; ``--out`` wr
 ``<stem>_label.png`` (train ids, or the dataset's own ids with ``--label-ids``) and, on request,
 ``<stem>_colour.png``.  ``--synthetic N --native-height Hn --native-width Wn`` does the same on the
 procedural dataset drawn at the native size."""
+import functools
 import json
 import os
-from argparse import ArgumentParser
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import _fullres_lib
-from .predict import MAX_PNG_THREADS, _save_png, default_palette
+from . import _head_common as hc
+from .predict import default_palette
 
 # train id -> the dataset's own label id, the ignore class (last) -> 0
 LABEL_IDS = {
@@ -31,16 +31,8 @@ LABEL_IDS = {
 }
 
 
-def _chk(t, name, dtype=torch.float32):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-        got = (f"{t.dtype}, {t.device}, contiguous={t.is_contiguous()}" if isinstance(t, torch.Tensor)
-               else type(t).__name__)
-        raise RuntimeError(f"mdil fullres_head: {name} must be a contiguous {str(dtype)[6:]} device tensor "
-                           f"(got {got}); there is no CPU fallback in the full-resolution path")
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
+_FN, _PATH = "fullres_head", "full-resolution"
+_chk = functools.partial(hc.chk, _FN, _PATH)
 
 
 def fullres_head(features, weight, bias, out_size, *, id_map=None, palette=None, target=None, ignore_index=-1,
@@ -59,49 +51,18 @@ def fullres_head(features, weight, bias, out_size, *, id_map=None, palette=None,
     _chk(weight, "weight")
     _chk(bias, "bias")
     x, w, b = features, weight, bias
-    if x.dim() != 4 or x.shape[3] != 16 or x.numel() == 0 or w.dim() != 4 or w.shape[0] != 16 \
-            or tuple(w.shape[2:]) != (2, 2) or b.numel() != w.shape[1]:
-        raise RuntimeError("mdil fullres_head: expects NHWC features [N,H,W,16] and ConvTranspose2d(16, nc, 2, 2) "
-                           f"parameters (got x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(b.shape)})")
-    N, H, W, nc = x.shape[0], x.shape[1], x.shape[2], w.shape[1]
-    if not _fullres_lib.MIN_CLASSES <= nc <= _fullres_lib.MAX_CLASSES:
-        raise RuntimeError(f"mdil fullres_head: {nc} classes (supported: {_fullres_lib.MIN_CLASSES} to "
-                           f"{_fullres_lib.MAX_CLASSES})")
-    if w.device != x.device or b.device != x.device:
-        raise RuntimeError(f"mdil fullres_head: features on {x.device}, weight on {w.device}, bias on {b.device}")
-    try:
-        Ho, Wo = (int(v) for v in out_size)
-    except (TypeError, ValueError):
-        raise RuntimeError(f"mdil fullres_head: out_size must be (height, width), got {out_size!r}") from None
-    if not (1 <= Ho <= _fullres_lib.MAX_SIZE and 1 <= Wo <= _fullres_lib.MAX_SIZE):
-        raise RuntimeError(f"mdil fullres_head: out_size {Ho} x {Wo} outside [1, {_fullres_lib.MAX_SIZE}]")
-    for t, name, shape in ((id_map, "id_map", (nc,)), (palette, "palette", (nc, 3)), (target, "target", (N, Ho, Wo))):
-        if t is not None:
-            _chk(t, name, torch.uint8)
-            if tuple(t.shape) != shape or t.device != x.device:
-                raise RuntimeError(f"mdil fullres_head: {name} must be uint8 {list(shape)} on {x.device} "
-                                   f"(got {tuple(t.shape)} on {t.device})")
-    if target is None:
-        if confusion is not None or bad_targets is not None:
-            raise RuntimeError("mdil fullres_head: confusion / bad_targets given without a target")
-    else:
-        if confusion is None or bad_targets is None:
-            raise RuntimeError("mdil fullres_head: a target needs confusion (int64 [nc,nc]) and bad_targets "
-                               "(int64 [1]) on the device; they are accumulated into")
-        for t, name, shape in ((confusion, "confusion", (nc, nc)), (bad_targets, "bad_targets", (1,))):
-            _chk(t, name, torch.int64)
-            if tuple(t.shape) != shape or t.device != x.device:
-                raise RuntimeError(f"mdil fullres_head: {name} must be int64 {list(shape)} on {x.device} "
-                                   f"(got {tuple(t.shape)} on {t.device})")
-    if not -1 <= int(ignore_index) <= 255:
-        raise RuntimeError(f"mdil fullres_head: ignore_index {ignore_index} outside [-1, 255]")
+    nc = hc.check_params(_FN, w, b, x)
+    N, H, W = x.shape[0], x.shape[1], x.shape[2]
+    hc.check_classes(_FN, _fullres_lib, nc, x, w, b)
+    Ho, Wo = hc.check_out_size(_FN, _fullres_lib, out_size)
+    hc.check_scoring(_FN, _PATH, x.device, N, nc, Ho, Wo, id_map, palette, target, confusion, bad_targets, ignore_index)
     with torch.no_grad(), torch.cuda.device(x.device):
         label = torch.empty(N, Ho, Wo, dtype=torch.uint8, device=x.device)
         colour = None if palette is None else torch.empty(N, Ho, Wo, 3, dtype=torch.uint8, device=x.device)
         _fullres_lib.check(
-            lib.mdil_fullres_head(x.data_ptr(), w.data_ptr(), b.data_ptr(), N, H, W, nc, Ho, Wo, _p(id_map),
-                                  _p(palette), _p(target), int(ignore_index), label.data_ptr(), _p(colour),
-                                  _p(confusion), _p(bad_targets),
+            lib.mdil_fullres_head(x.data_ptr(), w.data_ptr(), b.data_ptr(), N, H, W, nc, Ho, Wo, hc.ptr(id_map),
+                                  hc.ptr(palette), hc.ptr(target), int(ignore_index), label.data_ptr(),
+                                  hc.ptr(colour), hc.ptr(confusion), hc.ptr(bad_targets),
                                   torch.cuda.current_stream(x.device).cuda_stream),
             "mdil_fullres_head")
     return label, colour
@@ -122,6 +83,7 @@ class ConfusionMeter:
     the device by the fused kernel and scored by the reference's ``iouEval`` rule."""
 
     def __init__(self, nc, ignore_index):
+        self._name, self._model_fn, self._head_fn = "ConfusionMeter", predict_fullres, fullres_head
         self.nc, self.ignore_index = int(nc), int(ignore_index)
         self.confusion = self.bad_targets = None
 
@@ -130,13 +92,13 @@ class ConfusionMeter:
         ``target``: u8 [N,Ho,Wo] train ids on the device, which also sets the output size.
         -> (label, colour or None) of that call."""
         if not isinstance(target, torch.Tensor) or target.dim() != 3:
-            raise RuntimeError("mdil ConfusionMeter.add: target must be a uint8 [N,Ho,Wo] device tensor")
+            raise RuntimeError(f"mdil {self._name}.add: target must be a uint8 [N,Ho,Wo] device tensor")
         if self.confusion is None:
             self.confusion = torch.zeros(self.nc, self.nc, dtype=torch.int64, device=target.device)
             self.bad_targets = torch.zeros(1, dtype=torch.int64, device=target.device)
         kw.update(target=target, ignore_index=self.ignore_index, confusion=self.confusion,
                   bad_targets=self.bad_targets)
-        fn = predict_fullres if isinstance(source[0], torch.nn.Module) else fullres_head
+        fn = self._model_fn if isinstance(source[0], torch.nn.Module) else self._head_fn
         return fn(*source, tuple(target.shape[1:]), **kw)
 
     def matrix(self):
@@ -231,32 +193,20 @@ def _runs(shapes):
 
 
 def main(args):
-    from .models.erfnet_RA_parallel import Net as Net_RAP
-    from .trainer_common import _strip
     _refusals(args)
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
-    nb = len(args.num_classes)
-    if not 0 <= args.task < nb:
-        raise RuntimeError(f"--task {args.task}: the model has tasks 0 to {nb - 1}")
-    nc = args.num_classes[args.task]
-    model = Net_RAP(args.num_classes, nb, nb - 1)
-    saved = torch.load(args.state, map_location="cpu", weights_only=False)
-    model.load_state_dict(_strip(saved["state_dict"]), strict=True)
-    model.to(dev).eval()
+    dev, nc, model = hc.load_model(args)
     id_map = load_label_ids(args.label_ids, nc).to(dev) if args.label_ids else None
     palette = default_palette(nc).contiguous().to(dev) if args.colour else None
     meter = ConfusionMeter(nc, nc - 1) if args.score else None
     if args.out:
         os.makedirs(args.out, exist_ok=True)
     n_items, stems, sample = _open(args, nc)
-    written, pending = [], []
-    with ThreadPoolExecutor(max_workers=min(MAX_PNG_THREADS, os.cpu_count() or 1)) as pool:
+    with hc.png_pool() as pool:
+        png = hc.PngWriter(pool, args.out)
         for i0 in range(0, n_items, args.batch_size):
             idx = range(i0, min(i0 + args.batch_size, n_items))
             items = list(pool.map(sample, idx))
-            u8 = torch.from_numpy(np.stack([im for im, _ in items])).to(dev)        # [n,h,w,3] bytes
-            images = u8.permute(0, 3, 1, 2).to(torch.float32).div_(255.0)
+            images = hc.image_batch([im for im, _ in items], dev)
             with torch.no_grad():
                 feat = model.features(images, args.task).contiguous()
                 w, b = (t.detach() for t in model.head_params(args.task))
@@ -271,36 +221,16 @@ def main(args):
                     label, colour = fullres_head(feat[s:e], w, b, tuple(target.shape[1:]), **kw)
                 if args.out:
                     maps.append((s, label.cpu().numpy(), None if colour is None else colour.cpu().numpy()))
-            for f in pending:                  # the batch before this one: bounds what is in flight
-                f.result()
-            pending = []
+            png.wait()                         # the batch before this one: bounds what is in flight
             for s, label, colour in maps:
                 for k in range(label.shape[0]):
-                    jobs = [(label[k], f"{stems[idx[s + k]]}_label.png")]
+                    png.submit(label[k], f"{stems[idx[s + k]]}_label.png")
                     if colour is not None:
-                        jobs.append((colour[k], f"{stems[idx[s + k]]}_colour.png"))
-                    for arr, name in jobs:
-                        path = os.path.join(args.out, name)
-                        pending.append(pool.submit(_save_png, np.ascontiguousarray(arr), path))
-                        written.append(path)
-        for f in pending:
-            f.result()
+                        png.submit(colour[k], f"{stems[idx[s + k]]}_colour.png")
+        png.wait()
     report = {"dataset": "synthetic" if args.synthetic else args.dataset, "task": args.task, "images": n_items,
-              "written": written}
-    if meter is not None:
-        matrix = meter.matrix()
-        miou, per_class = meter.iou(matrix)
-        report.update(mIoU=float(miou), iou_classes=[float(v) for v in per_class], confusion=matrix.tolist(),
-                      pixels=int(matrix.sum()))
-        print(f"{report['dataset']} (task {args.task}) at the labels' own size: mIoU {float(miou) * 100:.2f} %  "
-              f"over {report['pixels']} pixels")
-        print("per-class IoU: " + " ".join(f"{float(v) * 100:.2f}" for v in per_class))
-    if args.out:
-        print(f"{len(written)} maps written to {args.out}")
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(report, f, indent=1)
-    return report
+              "written": png.written}
+    return hc.score_report(report, meter, args)
 
 
 def _refusals(args):
@@ -319,19 +249,9 @@ def _refusals(args):
         raise RuntimeError("sizes and --batch-size must be positive")
 
 
-class _Parser(ArgumentParser):
-    def parse_args(self, *a, **kw):
-        args = super().parse_args(*a, **kw)
-        try:
-            _refusals(args)
-        except RuntimeError as e:
-            self.error(str(e))
-        return args
-
-
-def build_parser():
+def add_flags(p, at_scale_1=""):
+    """The flags of this command line, which ``python -m mdil_ss_amd.ensemble`` shares."""
     from .dataset import add_datadir_flags
-    p = _Parser(description="label maps and mIoU at the dataset's own size from a checkpoint")
     p.add_argument("--state", required=True, help="checkpoint written by the trainers (or by the reference)")
     p.add_argument("--num-classes", type=int, nargs="+", required=True)
     p.add_argument("--task", type=int, required=True, help="which task's decoder predicts")
@@ -340,8 +260,8 @@ def build_parser():
     p.add_argument("--synthetic", type=int, default=0, help="N procedural images instead of a dataset")
     p.add_argument("--native-height", type=int, default=1024, help="--synthetic: the labels' own height")
     p.add_argument("--native-width", type=int, default=2048, help="--synthetic: the labels' own width")
-    p.add_argument("--height", type=int, default=512, help="the network's input height")
-    p.add_argument("--width", type=int, default=1024, help="the network's input width")
+    p.add_argument("--height", type=int, default=512, help="the network's input height" + at_scale_1)
+    p.add_argument("--width", type=int, default=1024, help="the network's input width" + at_scale_1)
     p.add_argument("--batch-size", type=int, default=6)
     p.add_argument("--score", action="store_true", help="mIoU and per-class IoU against the full-size labels")
     p.add_argument("--json", help="write the score (with the confusion matrix) here")
@@ -351,6 +271,11 @@ def build_parser():
                                        "JSON file with one id per class (default: train ids)")
     add_datadir_flags(p)
     return p
+
+
+def build_parser():
+    return add_flags(hc.RefusingParser(_refusals, description="label maps and mIoU at the dataset's own size from a "
+                                                             "checkpoint"))
 
 
 if __name__ == "__main__":

@@ -9,18 +9,21 @@ decoder's 16-channel features, so the logits are never stored (include/mdil_pred
 writes ``<stem>_label.png`` (8-bit train ids) and, on request, ``<stem>_colour.png`` (RGB) and
 ``<stem>_conf.png`` (``round(255 p)`` of the winning class).  ``--synthetic N`` predicts on the
 procedural dataset instead of a folder."""
+import functools
 import json
 import os
 from argparse import ArgumentParser
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
+from . import _head_common as hc
 from . import _predict_lib
+from ._head_common import MAX_PNG_THREADS, _save_png  # noqa: F401  (imported from here by users)
 from .transform import colormap, colormap_cityscapes
 
-MAX_PNG_THREADS = 16
+_FN, _PATH = "predict_head", "prediction"
+_chk = functools.partial(hc.chk, _FN, _PATH)
 
 
 def default_palette(nc):
@@ -34,18 +37,6 @@ def default_palette(nc):
     return torch.from_numpy(np.ascontiguousarray(cmap))
 
 
-def _chk(t, name, dtype=torch.float32):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-        got = (f"{t.dtype}, {t.device}, contiguous={t.is_contiguous()}" if isinstance(t, torch.Tensor)
-               else type(t).__name__)
-        raise RuntimeError(f"mdil predict_head: {name} must be a contiguous {str(dtype)[6:]} device tensor "
-                           f"(got {got}); there is no CPU fallback in the prediction path")
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 def predict_head(features, weight, bias, palette=None, want_confidence=False):
     """``output_conv`` + argmax on NHWC decoder features [N,H,W,16] and the
     ``ConvTranspose2d(16, nc, 2, 2)`` parameters, 2 <= nc <= 32, on the current stream.
@@ -56,28 +47,17 @@ def predict_head(features, weight, bias, palette=None, want_confidence=False):
     _chk(weight, "weight")
     _chk(bias, "bias")
     x, w, b = features, weight, bias
-    if x.dim() != 4 or x.shape[3] != 16 or x.numel() == 0 or w.dim() != 4 or w.shape[0] != 16 \
-            or tuple(w.shape[2:]) != (2, 2) or b.numel() != w.shape[1]:
-        raise RuntimeError("mdil predict_head: expects NHWC features [N,H,W,16] and ConvTranspose2d(16, nc, 2, 2) "
-                           f"parameters (got x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(b.shape)})")
-    N, H, W, nc = x.shape[0], x.shape[1], x.shape[2], w.shape[1]
-    if not _predict_lib.MIN_CLASSES <= nc <= _predict_lib.MAX_CLASSES:
-        raise RuntimeError(f"mdil predict_head: {nc} classes (supported: {_predict_lib.MIN_CLASSES} to "
-                           f"{_predict_lib.MAX_CLASSES})")
-    if w.device != x.device or b.device != x.device:
-        raise RuntimeError(f"mdil predict_head: features on {x.device}, weight on {w.device}, bias on {b.device}")
-    if palette is not None:
-        _chk(palette, "palette", torch.uint8)
-        if tuple(palette.shape) != (nc, 3) or palette.device != x.device:
-            raise RuntimeError(f"mdil predict_head: palette must be uint8 [{nc}, 3] on {x.device} "
-                               f"(got {tuple(palette.shape)} on {palette.device})")
+    nc = hc.check_params(_FN, w, b, x)
+    N, H, W = x.shape[0], x.shape[1], x.shape[2]
+    hc.check_classes(_FN, _predict_lib, nc, x, w, b)
+    hc.check_tables(_FN, _PATH, x.device, torch.uint8, ((palette, "palette", (nc, 3)),))
     with torch.no_grad(), torch.cuda.device(x.device):
         label = torch.empty(N, 2 * H, 2 * W, dtype=torch.uint8, device=x.device)
         colour = None if palette is None else torch.empty(N, 2 * H, 2 * W, 3, dtype=torch.uint8, device=x.device)
         conf = torch.empty(N, 2 * H, 2 * W, dtype=torch.float32, device=x.device) if want_confidence else None
         _predict_lib.check(
-            lib.mdil_predict_head(x.data_ptr(), w.data_ptr(), b.data_ptr(), N, H, W, nc, _p(palette),
-                                  label.data_ptr(), _p(colour), _p(conf),
+            lib.mdil_predict_head(x.data_ptr(), w.data_ptr(), b.data_ptr(), N, H, W, nc, hc.ptr(palette),
+                                  label.data_ptr(), hc.ptr(colour), hc.ptr(conf),
                                   torch.cuda.current_stream(x.device).cuda_stream),
             "mdil_predict_head")
     return label, colour, conf
@@ -113,11 +93,6 @@ def _load_resized(path, height, width):
         return np.asarray(im.convert("RGB").resize((width, height), Image.BILINEAR), dtype=np.uint8)
 
 
-def _save_png(arr, path):
-    from PIL import Image
-    Image.fromarray(arr).save(path)
-
-
 def _batches(args, nc, pool, dev):
     """-> (stems, images f32 [n,3,H,W] on the device) per batch."""
     bs = args.batch_size
@@ -131,23 +106,11 @@ def _batches(args, nc, pool, dev):
     files, stems = _image_files(args.images)
     for i in range(0, len(files), bs):
         arrs = list(pool.map(lambda f: _load_resized(f, args.height, args.width), files[i:i + bs]))
-        u8 = torch.from_numpy(np.stack(arrs)).to(dev)                       # [n,H,W,3] bytes
-        yield stems[i:i + bs], u8.permute(0, 3, 1, 2).to(torch.float32).div_(255.0)
+        yield stems[i:i + bs], hc.image_batch(arrs, dev)
 
 
 def main(args):
-    from .models.erfnet_RA_parallel import Net as Net_RAP
-    from .trainer_common import _strip
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(dev)
-    nb = len(args.num_classes)
-    if not 0 <= args.task < nb:
-        raise RuntimeError(f"--task {args.task}: the model has tasks 0 to {nb - 1}")
-    nc = args.num_classes[args.task]
-    model = Net_RAP(args.num_classes, nb, nb - 1)
-    saved = torch.load(args.state, map_location="cpu", weights_only=False)
-    model.load_state_dict(_strip(saved["state_dict"]), strict=True)
-    model.to(dev).eval()
+    dev, nc, model = hc.load_model(args)
     palette = None
     if args.colour:
         if args.palette:
@@ -159,8 +122,8 @@ def main(args):
             palette = default_palette(nc)
         palette = palette.contiguous().to(dev)
     os.makedirs(args.out, exist_ok=True)
-    written, pending = [], []
-    with ThreadPoolExecutor(max_workers=min(MAX_PNG_THREADS, os.cpu_count() or 1)) as pool:
+    with hc.png_pool() as pool:
+        png = hc.PngWriter(pool, args.out)
         for stems, images in _batches(args, nc, pool, dev):
             label, colour, conf = predict(model, images, args.task, palette, args.confidence)
             # one device-to-host copy per batch: every requested map as bytes, channels side by side
@@ -170,25 +133,18 @@ def main(args):
             if conf is not None:
                 planes.append(conf.mul(255.0).round_().nan_to_num_(0.0).clamp_(0.0, 255.0).to(torch.uint8).unsqueeze(3))
             host = (torch.cat(planes, 3) if len(planes) > 1 else planes[0]).cpu().numpy()
-            for f in pending:                  # the batch before this one: bounds what is in flight
-                f.result()
-            pending = []
+            png.wait()                         # the batch before this one: bounds what is in flight
             for k, stem in enumerate(stems):
-                jobs = [(np.ascontiguousarray(host[k, :, :, 0]), f"{stem}_label.png")]
+                png.submit(host[k, :, :, 0], f"{stem}_label.png")
                 c = 1
                 if colour is not None:
-                    jobs.append((np.ascontiguousarray(host[k, :, :, 1:4]), f"{stem}_colour.png"))
+                    png.submit(host[k, :, :, 1:4], f"{stem}_colour.png")
                     c = 4
                 if conf is not None:
-                    jobs.append((np.ascontiguousarray(host[k, :, :, c]), f"{stem}_conf.png"))
-                for arr, name in jobs:
-                    path = os.path.join(args.out, name)
-                    pending.append(pool.submit(_save_png, arr, path))
-                    written.append(path)
-        for f in pending:
-            f.result()
-    print(f"{len(written)} maps written to {args.out}")
-    return written
+                    png.submit(host[k, :, :, c], f"{stem}_conf.png")
+        png.wait()
+    print(f"{len(png.written)} maps written to {args.out}")
+    return png.written
 
 
 def build_parser():

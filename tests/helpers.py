@@ -175,3 +175,35 @@ def kernel_build_id():
                     body.append(ast.Pass())
         h.update(os.path.basename(f).encode() + b"\0" + ast.dump(tree, annotate_fields=False).encode() + b"\0")
     return h.hexdigest()[:12]
+
+
+# ------------------------------------------------------------- the add-on libraries' C ABI
+def declared_names(header):
+    """The mdil_* functions that ``include/<header>`` declares (comments left out)."""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hdr = open(os.path.join(root, "include", header)).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    return sorted(set(re.findall(r"\b(mdil_[a-z0-9_]+)\s*\(", hdr)))
+
+
+def dynamic_exports(path):
+    """Names of the defined, non-local symbols in an ELF64 (little-endian) shared object's .dynsym."""
+    import struct
+    data = open(path, "rb").read()
+    assert data[:4] == b"\x7fELF" and data[4] == 2 and data[5] == 1, "not a little-endian ELF64 file"
+    shoff, = struct.unpack_from("<Q", data, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + i * shentsize) for i in range(shnum)]
+    names = []
+    for _, sh_type, _, _, off, size, link, _, _, entsize in sections:
+        if sh_type != 11:                                   # SHT_DYNSYM
+            continue
+        str_off = sections[link][4]
+        for k in range(1, size // entsize):
+            st_name, st_info, _, st_shndx, _, _ = struct.unpack_from("<IBBHQQ", data, off + k * entsize)
+            if st_shndx != 0 and (st_info >> 4) in (1, 2):  # defined; STB_GLOBAL or STB_WEAK
+                end = data.index(b"\0", str_off + st_name)
+                names.append(data[str_off + st_name:end].decode())
+    return sorted(names)

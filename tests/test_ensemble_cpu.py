@@ -5,41 +5,34 @@ states, every argument check answers before any launch, the command line's defau
 the refusal of host tensors, and the rule every add-on exists under: the training path's build id
 stays where the recorded runs have it."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from tests import ensemble_reference as R
-from tests.test_fullres_cpu import _dynamic_exports
+from tests.helpers import declared_names, dynamic_exports
 
 REPO = R.REPO
 NAMES = ["mdil_ensemble_head", "mdil_ensemble_last_error", "mdil_ensemble_version"]
-
-
-def _declared():
-    hdr = open(os.path.join(REPO, "include", "mdil_ensemble.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(mdil_[a-z0-9_]+)\s*\(", hdr)))
 
 
 def test_library_exports_exactly_the_declared_symbols():
     import mdil_ss_amd  # noqa: F401
     from mdil_ss_amd import _ensemble_lib, _fullres_lib, _lib, _predict_lib
     lib = _ensemble_lib.load()
-    assert _declared() == NAMES
+    assert declared_names("mdil_ensemble.h") == NAMES
     for n in NAMES:
         assert hasattr(lib, n), f"{n} declared in include/mdil_ensemble.h but not exported"
     assert sorted(_ensemble_lib.EXPORTS) == NAMES
-    assert _dynamic_exports(_ensemble_lib.LIB_PATH) == NAMES
+    assert dynamic_exports(_ensemble_lib.LIB_PATH) == NAMES
     assert lib.mdil_ensemble_version() >= 100
     # the other three keep their names
-    assert _dynamic_exports(_fullres_lib.LIB_PATH) == ["mdil_fullres_head", "mdil_fullres_last_error",
+    assert dynamic_exports(_fullres_lib.LIB_PATH) == ["mdil_fullres_head", "mdil_fullres_last_error",
                                                        "mdil_fullres_version"]
-    assert _dynamic_exports(_predict_lib.LIB_PATH) == ["mdil_predict_head", "mdil_predict_last_error",
+    assert dynamic_exports(_predict_lib.LIB_PATH) == ["mdil_predict_head", "mdil_predict_last_error",
                                                        "mdil_predict_version"]
-    assert set(_lib.EXPORTS) <= set(_dynamic_exports(_lib.LIB_PATH))
+    assert set(_lib.EXPORTS) <= set(dynamic_exports(_lib.LIB_PATH))
 
 
 def test_header_states_the_constants():

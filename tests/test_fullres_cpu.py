@@ -4,55 +4,29 @@ command line's defaults and refusals, the iouEval rule of ConfusionMeter, the Ci
 the refusal of host tensors, and the rule the add-on exists under: it leaves the training path's
 build id alone."""
 import os
-import re
-import struct
 
 import numpy as np
 import pytest
 import torch
 
+from tests.helpers import declared_names, dynamic_exports
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ["mdil_fullres_head", "mdil_fullres_last_error", "mdil_fullres_version"]
-
-
-def _declared():
-    hdr = open(os.path.join(REPO, "include", "mdil_fullres.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(mdil_[a-z0-9_]+)\s*\(", hdr)))
-
-
-def _dynamic_exports(path):
-    """Names of the defined, non-local symbols in an ELF64 (little-endian) shared object's .dynsym."""
-    data = open(path, "rb").read()
-    assert data[:4] == b"\x7fELF" and data[4] == 2 and data[5] == 1, "not a little-endian ELF64 file"
-    shoff, = struct.unpack_from("<Q", data, 0x28)
-    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
-    sections = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + i * shentsize) for i in range(shnum)]
-    names = []
-    for _, sh_type, _, _, off, size, link, _, _, entsize in sections:
-        if sh_type != 11:                                   # SHT_DYNSYM
-            continue
-        str_off = sections[link][4]
-        for k in range(1, size // entsize):
-            st_name, st_info, _, st_shndx, _, _ = struct.unpack_from("<IBBHQQ", data, off + k * entsize)
-            if st_shndx != 0 and (st_info >> 4) in (1, 2):  # defined; STB_GLOBAL or STB_WEAK
-                end = data.index(b"\0", str_off + st_name)
-                names.append(data[str_off + st_name:end].decode())
-    return sorted(names)
 
 
 def test_library_exports_exactly_the_declared_symbols():
     import mdil_ss_amd  # noqa: F401
     from mdil_ss_amd import _fullres_lib, _predict_lib
     lib = _fullres_lib.load()
-    assert _declared() == NAMES
+    assert declared_names("mdil_fullres.h") == NAMES
     for n in NAMES:
         assert hasattr(lib, n), f"{n} declared in include/mdil_fullres.h but not exported"
     assert sorted(_fullres_lib.EXPORTS) == NAMES
-    assert _dynamic_exports(_fullres_lib.LIB_PATH) == NAMES
+    assert dynamic_exports(_fullres_lib.LIB_PATH) == NAMES
     assert lib.mdil_fullres_version() >= 100
     # the first add-on keeps its three names
-    assert _dynamic_exports(_predict_lib.LIB_PATH) == ["mdil_predict_head", "mdil_predict_last_error",
+    assert dynamic_exports(_predict_lib.LIB_PATH) == ["mdil_predict_head", "mdil_predict_last_error",
                                                        "mdil_predict_version"]
 
 

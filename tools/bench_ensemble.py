@@ -19,9 +19,7 @@ HBM peak; peak memory is the allocator's high-water mark of one call above what 
 before it.  The fused call must come out faster than the unfused route and its peak memory below
 one view's resized logits: the tool fails otherwise.  No GPU: it fails, it does not fall back."""
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
@@ -29,7 +27,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from tools.bench_fullres import HBM_PEAK, peak_bytes, timed  # noqa: E402
+from tools._bench_common import peak_bytes, timed, variant_rows, write_report  # noqa: E402
 
 
 def main():
@@ -119,13 +117,7 @@ def main():
         bytes_moved[f"unfused {mode} from stored logits: label"] = route
         bytes_moved[f"unfused {mode} from stored logits: label + confusion"] = route + npo * (1 + 8 + 8 + 8)
     bytes_moved[f"{nv} x fullres_head: labels"] = feat_b + nv * npo
-    rows = {}
-    for k, v in samples.items():
-        med = statistics.median(v)
-        rows[k] = {"us_median": round(med, 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1),
-                   "algorithmic_bytes": bytes_moved[k],
-                   "share_of_hbm_peak": round(bytes_moved[k] / (med * 1e-6) / HBM_PEAK, 4),
-                   "peak_memory_bytes": peaks[k]}
+    rows = variant_rows(samples, bytes_moved, peaks)
     yard = rows[f"{nv} x fullres_head: labels"]["us_median"]
     report = {
         "shape": {"batch": N, "features": [list(s) for s in shapes], "flip": not args.no_flip, "views": nv,
@@ -142,12 +134,7 @@ def main():
                                       for mode in ("prob", "logit")},
         "labels_differing_between_routes": differ,
     }
-    print(json.dumps(report))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(report, f, indent=1)
-            f.write("\n")
+    write_report(report, args.out)
     for mode in ("prob", "logit"):
         for kind in ("label", "label + confusion"):
             fused, unf = rows[f"fused {mode}: {kind}"], rows[f"unfused {mode} from stored logits: {kind}"]

@@ -15,9 +15,7 @@ Bytes are what each route must move, computed from the shapes, over the median t
 the 8 TB/s HBM peak; peak memory is the allocator's high-water mark of one call above what was
 allocated before it.  No GPU: it fails, it does not fall back."""
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
@@ -25,29 +23,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-HBM_PEAK = 8.0e12                                                     # bytes / s
-
-
-def timed(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) * 1e3 / iters                      # us per call
-
-
-def peak_bytes(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    before = torch.cuda.memory_allocated()
-    out = fn()
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - before
-    del out
-    return peak
+from tools._bench_common import peak_bytes, timed, variant_rows, write_report  # noqa: E402
 
 
 def main():
@@ -128,13 +104,7 @@ def main():
         stored_route = lg_b + 2 * up_b + npo * 12 + unf_extra[kind]
         bytes_moved[f"unfused from stored logits: {kind}"] = stored_route
         bytes_moved[f"unfused from features: {kind}"] = stored_route + npf * 64 + lg_b
-    rows = {}
-    for k, v in samples.items():
-        med = statistics.median(v)
-        rows[k] = {"us_median": round(med, 1), "us_min": round(min(v), 1), "us_max": round(max(v), 1),
-                   "algorithmic_bytes": bytes_moved[k],
-                   "share_of_hbm_peak": round(bytes_moved[k] / (med * 1e-6) / HBM_PEAK, 4),
-                   "peak_memory_bytes": peaks[k]}
+    rows = variant_rows(samples, bytes_moved, peaks)
     report = {
         "shape": {"batch": N, "feature_height": H, "feature_width": W, "out_height": Ho, "out_width": Wo, "classes": nc},
         "device": torch.cuda.get_device_name(0),
@@ -143,12 +113,7 @@ def main():
         "fused_fma_per_call": npo * nc * 64,
         "labels_differing_between_routes": differ,
     }
-    print(json.dumps(report))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(report, f, indent=1)
-            f.write("\n")
+    write_report(report, args.out)
 
 
 if __name__ == "__main__":

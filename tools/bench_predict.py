@@ -9,9 +9,7 @@ the variants alternate over ``--rounds`` rounds and each reports its median and 
 rows time the head alone on precomputed decoder features; ``net`` rows the whole forward.  Bytes
 are what the algorithm must move, computed from the shapes.  No GPU: it fails, it does not fall back."""
 import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
@@ -19,14 +17,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def timed(fn, iters):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end) * 1e3 / iters                      # us per call
+from tools._bench_common import spread, timed, write_report  # noqa: E402
 
 
 def main():
@@ -76,8 +67,7 @@ def main():
     report = {
         "shape": {"batch": N, "height": H, "width": W, "classes": nc},
         "device": torch.cuda.get_device_name(0),
-        "us_per_call": {k: {"median": round(statistics.median(v), 2), "min": round(min(v), 2),
-                            "max": round(max(v), 2)} for k, v in samples.items()},
+        "us_per_call": {k: spread(v, 2, "") for k, v in samples.items()},
         "algorithmic_bytes": {
             "features read": npix * 64,
             "fused maps written (label / + colour / + confidence)": [npix * 4, npix * 16, npix * 32],
@@ -86,13 +76,7 @@ def main():
         },
         "labels_differing_between_paths": differ,
     }
-    line = json.dumps(report)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(report, f, indent=1)
-            f.write("\n")
+    write_report(report, args.out)
 
 
 if __name__ == "__main__":
