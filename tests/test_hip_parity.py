@@ -68,7 +68,9 @@ def rnd(*shape, seed=0, scale=1.0):
 @pytest.mark.parametrize("C,H,W,d,kind", [
     (64, 12, 20, 1, "3x1"), (64, 12, 20, 1, "1x3"), (128, 9, 16, 2, "3x1"), (128, 9, 16, 4, "1x3"),
     (128, 20, 24, 16, "1x3"), (128, 20, 24, 16, "3x1"), (16, 10, 36, 1, "3x1"), (16, 10, 36, 1, "1x3"),
-    # ragged last tiles / many tiles per wave of the streaming kernels
+    # ragged last tiles of the streaming kernels.  (25,220 px at C=128, 33,540 px at C=64: on a 256-CU device
+    # every wave still runs exactly ONE tile here -- several tiles per wave, with the ragged tile in a later
+    # round, are compared with a reference in tests/test_streaming_multitile_gpu.py)
     (128, 97, 130, 16, "3x1"), (128, 97, 130, 2, "1x3"), (64, 130, 129, 1, "3x1"), (64, 130, 129, 1, "1x3"),
     # W % 16 == 0: the streaming weight-gradient kernel (row descriptors, 16-pixel quads)
     (64, 12, 32, 1, "3x1"), (64, 12, 32, 1, "1x3"), (128, 20, 48, 16, "3x1"), (128, 20, 48, 16, "1x3"),
@@ -150,8 +152,16 @@ def _grad_check(S_cpu, S_dev, names, what):
                                          (128, 40, 64, 4, True), (64, 24, 48, 1, False)])
 @pytest.mark.parametrize("train", [True, False])
 def test_nb_block(dev, C, H, W, d, rap, train):
+    nb_block_case(dev, C, H, W, d, rap, train)
+
+
+def nb_block_case(dev, C, H, W, d, rap, train, N=2, run=None):
+    """One factorised block, forward (+ backward in train mode), against the oracle's functional block.
+    ``run`` (tests/test_streaming_multitile_gpu.py): called as ``run(fn)`` around the HIP forward and the
+    HIP backward, so a caller can watch which launches they make."""
     from mdil_ss_amd import ops
-    N = 2
+    if run is None:
+        run = lambda fn: fn()
     p = "blk"
     S = {}
     for i, (kk, nm) in enumerate([((3, 1), "conv3x1_1"), ((1, 3), "conv1x3_1"), ((3, 1), "conv3x1_2"),
@@ -181,13 +191,16 @@ def test_nb_block(dev, C, H, W, d, rap, train):
     bufs = tuple(Sd[f"{b}.{s}"] for b in (bn1, bn2) for s in ("running_mean", "running_var", "num_batches_tracked"))
     pw = (lambda j, s: Sd[f"{p}.parallel_conv_{j}.0.{s}"]) if rap else (lambda j, s: None)
     ops.GATE_LOG = [] if train else None
-    got = ops.NbFn.apply(xd, Sd[f"{p}.conv3x1_1.weight"], Sd[f"{p}.conv3x1_1.bias"],
-                         Sd[f"{p}.conv1x3_1.weight"], Sd[f"{p}.conv1x3_1.bias"], pw(1, "weight"),
-                         pw(1, "bias"), Sd[bn1 + ".weight"], Sd[bn1 + ".bias"],
-                         Sd[f"{p}.conv3x1_2.weight"], Sd[f"{p}.conv3x1_2.bias"],
-                         Sd[f"{p}.conv1x3_2.weight"], Sd[f"{p}.conv1x3_2.bias"], pw(2, "weight"),
-                         pw(2, "bias"), Sd[bn2 + ".weight"], Sd[bn2 + ".bias"], bufs,
-                         None if mask is None else mask.reshape(N, C).to(dev), d, train, None, None)
+    drop = None if mask is None else mask.reshape(N, C).to(dev)
+    res = []
+    run(lambda: res.append(ops.NbFn.apply(
+        xd, Sd[f"{p}.conv3x1_1.weight"], Sd[f"{p}.conv3x1_1.bias"],
+        Sd[f"{p}.conv1x3_1.weight"], Sd[f"{p}.conv1x3_1.bias"], pw(1, "weight"),
+        pw(1, "bias"), Sd[bn1 + ".weight"], Sd[bn1 + ".bias"],
+        Sd[f"{p}.conv3x1_2.weight"], Sd[f"{p}.conv3x1_2.bias"],
+        Sd[f"{p}.conv1x3_2.weight"], Sd[f"{p}.conv1x3_2.bias"], pw(2, "weight"),
+        pw(2, "bias"), Sd[bn2 + ".weight"], Sd[bn2 + ".bias"], bufs, drop, d, train, None, None)))
+    got = res[0]
     # train mode: the oracle replays the ReLU gates the HIP forward took (ops.GATE_LOG), so the
     # backward comparison below is element-wise tight for every tensor -- no allowance for
     # pre-activations that round to different sides of zero in the two implementations
@@ -206,7 +219,8 @@ def test_nb_block(dev, C, H, W, d, rap, train):
                 close(Sd[f"{b}.{s_}"].float(), S[f"{b}.{s_}"].float(), what=f"{what} {b}.{s_}")
         go = rnd(*want.shape, seed=6)
         want.backward(go)
-        got.backward(nhwc(go).to(dev))
+        god = nhwc(go).to(dev)
+        run(lambda: got.backward(god))
         close(nchw(xd.grad), xc.grad, rtol=1e-3, atol=1e-4, what=what + " gx")
         _grad_check(S, Sd, names, what)
     ops.invalidate_packs()
@@ -304,7 +318,14 @@ def test_three_tap_conv_and_weight_gradient_winograd_shapes(dev, C, H, W, d, axi
     taps = ops._taps_1x3(d) if axis == "w" else ops._taps_3x1(d)
     g = ops.make_geom(N, H, W, H, W, taps, C, H, W, C)
     xd, wd, bd, gd = nhwc(x).to(dev), w.to(dev), b.to(dev), nhwc(go).to(dev)
-    out = ops.tapconv(g, C, C, xd, None, ops.pack_conv(wd, "fwd"), torch.empty_like(xd), bias=bd)
+    # the kernel the case is about really takes the launch (a change of wconv_plan, or an MDIL_NO_* variable
+    # in the environment, must not turn this into a test of another kernel)
+    from tests.streaming_tiles import paths
+    L = W if axis == "w" else H
+    family = "w4conv" if L % (4 * d) == 0 else "wconv" if L % (2 * d) == 0 else "sconv"
+    assert (family == "sconv") == ((C, H, W, d, axis) == (128, 20, 32, 16, "h"))      # the one direct-form case
+    wpk, out = ops.pack_conv(wd, "fwd"), torch.empty_like(xd)
+    assert paths(lambda: ops.tapconv(g, C, C, xd, None, wpk, out, bias=bd)) == [family], (C, H, W, d, axis)
     close(nchw(out), want.float(), what=f"conv {axis} d{d} fwd")
     dw, db = ops.wgrad(g, C, C, xd, None, gd, (0, 1, 2), C * 3, 3, wd, bd)
     close(dw, wr.grad.float(), rtol=1e-4, atol=2e-5, what=f"conv {axis} d{d} dW")
@@ -312,7 +333,8 @@ def test_three_tap_conv_and_weight_gradient_winograd_shapes(dev, C, H, W, d, axi
     # dgrad = the same kernel on mirrored taps
     gt = ops.make_geom(N, H, W, H, W, ops._taps_1x3(d, flip=True) if axis == "w" else ops._taps_3x1(d, flip=True),
                        C, H, W, C)
-    gx = ops.tapconv(gt, C, C, gd, None, ops.pack_conv(wd, "dgrad"), torch.empty_like(xd))
+    wpk_t, gx = ops.pack_conv(wd, "dgrad"), torch.empty_like(xd)
+    assert paths(lambda: ops.tapconv(gt, C, C, gd, None, wpk_t, gx)) == [family], (C, H, W, d, axis, "dgrad")
     close(nchw(gx), xr.grad.float(), what=f"conv {axis} d{d} dgrad")
     ops.invalidate_packs()
 
