@@ -1,7 +1,8 @@
-"""What the three inference drivers (predict.py, fullres.py, ensemble.py) share: the argument checks
-of their ``*_head`` entry points -- each takes the entry point's name, so every message reads as it
-always did -- the checkpoint loader, the byte batch -> image tensor step, the bounded PNG writer and
-the score report of their command lines."""
+"""What the head drivers share (predict.py, fullres.py, ensemble.py and, with _report_common.py on
+top, drift.py and calibrate.py; latent.py and similarity.py take the loader and the parser): the
+argument checks of their ``*_head`` entry points -- each takes the entry point's name, so every
+message reads as it always did -- the checkpoint loader, the byte batch -> image tensor step, the
+bounded PNG writer and the score report of the inference command lines."""
 import json
 import os
 from argparse import ArgumentParser
@@ -82,6 +83,10 @@ def check_scoring(fn, path, dev, N, nc, Ho, Wo, id_map, palette, target, confusi
                                "(int64 [1]) on the device; they are accumulated into")
         check_tables(fn, path, dev, torch.int64,
                      ((confusion, "confusion", (nc, nc)), (bad_targets, "bad_targets", (1,))))
+    check_ignore_index(fn, ignore_index)
+
+
+def check_ignore_index(fn, ignore_index):
     if not -1 <= int(ignore_index) <= 255:
         raise RuntimeError(f"mdil {fn}: ignore_index {ignore_index} outside [-1, 255]")
 
@@ -104,20 +109,20 @@ class RefusingParser(ArgumentParser):
         return args
 
 
-def load_model(args):
-    """-> (device, class count of ``args.task``, Net_RAP with ``args.state`` loaded, in eval mode)."""
+def load_model(state, num_classes, task):
+    """-> (device, class count of ``task``, Net_RAP(num_classes) with the checkpoint ``state`` loaded, in eval mode)."""
     from .models.erfnet_RA_parallel import Net as Net_RAP
     from .trainer_common import _strip
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    nb = len(args.num_classes)
-    if not 0 <= args.task < nb:
-        raise RuntimeError(f"--task {args.task}: the model has tasks 0 to {nb - 1}")
-    model = Net_RAP(args.num_classes, nb, nb - 1)
-    saved = torch.load(args.state, map_location="cpu", weights_only=False)
+    nb = len(num_classes)
+    if not 0 <= task < nb:
+        raise RuntimeError(f"--task {task}: the model has tasks 0 to {nb - 1}")
+    model = Net_RAP(num_classes, nb, nb - 1)
+    saved = torch.load(state, map_location="cpu", weights_only=False)
     model.load_state_dict(_strip(saved["state_dict"]), strict=True)
     model.to(dev).eval()
-    return dev, args.num_classes[args.task], model
+    return dev, num_classes[task], model
 
 
 def image_batch(arrays, dev):
@@ -166,6 +171,10 @@ def score_report(report, meter, args, how=""):
     if args.out:
         print(f"{len(report['written'])} maps written to {args.out}")
     if args.json:
-        with open(args.json, "w") as f:
-            json.dump(report, f, indent=1)
+        write_json(report, args.json)
     return report
+
+
+def write_json(report, path):
+    with open(path, "w") as f:
+        json.dump(report, f, indent=1)

@@ -17,7 +17,6 @@ happened.  ``--out`` writes ``reliability.png``: per bin the gap between accurac
 at T = 1 and at the fitted (or first given) temperature."""
 import ctypes as C
 import functools
-import json
 import math
 import os
 
@@ -25,6 +24,7 @@ import torch
 
 from . import _calib_lib
 from . import _head_common as hc
+from . import _report_common as rc
 
 _FN, _PATH = "calib_head", "calibration"
 _chk = functools.partial(hc.chk, _FN, _PATH)
@@ -75,8 +75,7 @@ def calib_head(feat, w, b, target, temps, *, bins=15, ignore_index=-1, class_tem
     if target is None:
         raise RuntimeError(f"mdil {_FN}: a target (uint8 [N,2H,2W] on the device) is required")
     hc.check_tables(_FN, _PATH, dev, torch.uint8, ((target, "target", (N, 2 * H, 2 * W)),))
-    if not -1 <= int(ignore_index) <= 255:
-        raise RuntimeError(f"mdil {_FN}: ignore_index {ignore_index} outside [-1, 255]")
+    hc.check_ignore_index(_FN, ignore_index)
     temps = _temperatures(temps)
     K, bins = len(temps), int(bins)
     if not 1 <= bins <= _calib_lib.MAX_BINS:
@@ -84,27 +83,14 @@ def calib_head(feat, w, b, target, temps, *, bins=15, ignore_index=-1, class_tem
     ct = -1 if class_temp is None else int(class_temp)
     if not -1 <= ct < K:
         raise RuntimeError(f"mdil {_FN}: class_temp {class_temp} is not an index into the {K} temperatures")
-    c = dict(counters or {})
-    unknown = sorted(set(c) - set(_COUNTERS))
-    if unknown:
-        raise RuntimeError(f"mdil {_FN}: unknown counters {unknown} (known: {list(_COUNTERS)})")
-    c = {k: c.get(k) for k in _COUNTERS}
+    c = rc.check_counters(_FN, counters, _COUNTERS)
     hc.check_tables(_FN, _PATH, dev, torch.int64,
                     ((c["hist"], "hist", (K, bins, 3)), (c["class_hist"], "class_hist", (nc, bins, 3)),
                      (c["nonfinite"], "nonfinite", (K,)), (c["bad_targets"], "bad_targets", (1,))))
     hc.check_tables(_FN, _PATH, dev, torch.float64, ((c["sums"], "sums", (K, 3)),))
     if c["class_hist"] is not None and ct < 0:
         raise RuntimeError(f"mdil {_FN}: class_hist needs class_temp, the index of the temperature it is taken at")
-    ws_bytes = 0
-    if c["sums"] is not None:
-        need = workspace_bytes(N, H, W, nc, K)
-        ws = c["workspace"]
-        if ws is None:
-            raise RuntimeError(f"mdil {_FN}: sums need a workspace (float64, {need} bytes) on the device")
-        _chk(ws, "workspace", torch.float64)
-        ws_bytes = ws.numel() * 8
-        if ws.device != dev or ws_bytes < need:
-            raise RuntimeError(f"mdil {_FN}: workspace must hold {need} bytes on {dev} (got {ws_bytes} on {ws.device})")
+    ws, ws_bytes = rc.check_workspace(_FN, _PATH, dev, c, lambda: workspace_bytes(N, H, W, nc, K))
     host_temps = (C.c_float * K)(*temps)
     with torch.no_grad(), torch.cuda.device(dev):
         out = {"label": torch.empty(N, 2 * H, 2 * W, dtype=torch.uint8, device=dev) if label else None,
@@ -114,8 +100,7 @@ def calib_head(feat, w, b, target, temps, *, bins=15, ignore_index=-1, class_tem
             lib.mdil_calib_head(feat.data_ptr(), w.data_ptr(), b.data_ptr(), N, H, W, nc, target.data_ptr(),
                                 int(ignore_index), host_temps, K, bins, ct, hc.ptr(out["label"]), hc.ptr(out["conf"]),
                                 hc.ptr(out["nll"]), hc.ptr(c["hist"]), hc.ptr(c["class_hist"]), hc.ptr(c["sums"]),
-                                hc.ptr(c["nonfinite"]), hc.ptr(c["bad_targets"]),
-                                hc.ptr(c["workspace"]) if c["sums"] is not None else None, ws_bytes,
+                                hc.ptr(c["nonfinite"]), hc.ptr(c["bad_targets"]), ws, ws_bytes,
                                 torch.cuda.current_stream(dev).cuda_stream),
             "mdil_calib_head")
     return out
@@ -151,30 +136,13 @@ class CalibrationMeter:
                             "sums": torch.zeros(K, 3, dtype=torch.float64, device=dev)}
             if self.class_temp is not None:
                 self.tensors["class_hist"] = z(self.nc, self.bins, 3)
-        need = workspace_bytes(N, H, W, self.nc, K) // 8
-        ws = self.tensors.get("workspace")
-        if ws is None or ws.numel() < need:
-            self.tensors["workspace"] = torch.empty(need, dtype=torch.float64, device=dev)
+        rc.grow_workspace(self.tensors, workspace_bytes(N, H, W, self.nc, K), dev)
         return self.tensors
 
     def add(self, *source, target=None, **kw):
         """``add(model, images, task, target=t)`` or ``add(feat, w, b, target=t)``, ``t`` u8 [N,2H,2W]
         train ids on the device.  -> ``calib_head``'s dict."""
-        if isinstance(source[0], torch.nn.Module):
-            images = source[1]
-            if not isinstance(images, torch.Tensor) or images.dim() != 4:
-                raise RuntimeError("mdil CalibrationMeter.add: images must be a float32 [N,3,H,W] device tensor")
-            dev, N, H, W = images.device, images.shape[0], images.shape[2] // 2, images.shape[3] // 2
-            fn = calibrate
-        else:
-            feat = source[0]
-            if not isinstance(feat, torch.Tensor) or feat.dim() != 4:
-                raise RuntimeError("mdil CalibrationMeter.add: feat must be NHWC features [N,H,W,16]")
-            dev, (N, H, W) = feat.device, feat.shape[:3]
-            fn = calib_head
-        if dev.type != "cuda":
-            raise RuntimeError("mdil CalibrationMeter.add: inputs must be device tensors; there is no CPU fallback in "
-                               "the calibration path")
+        fn, dev, N, H, W = rc.meter_source("CalibrationMeter", _PATH, source, 1, calibrate, calib_head, "feat")
         if target is None:
             raise RuntimeError("mdil CalibrationMeter.add: a target is required")
         return fn(*source, target, self.temps, bins=self.bins, ignore_index=self.ignore_index,
@@ -189,10 +157,7 @@ class CalibrationMeter:
             if self.class_temp is not None:
                 out["class_hist"] = torch.zeros(self.nc, self.bins, 3, dtype=torch.int64)
             return out
-        bad = int(self.tensors["bad_targets"].item())
-        if bad:
-            raise RuntimeError(f"mdil CalibrationMeter: {bad} target pixels are outside [0, {self.nc}) and are not the "
-                               f"ignore index {self.ignore_index}")
+        rc.refuse_bad_targets("CalibrationMeter", self.tensors, self.nc, self.ignore_index)
         nonfinite = self.tensors["nonfinite"].cpu().tolist()
         if any(nonfinite):
             raise RuntimeError(f"mdil CalibrationMeter: counted pixels with a non-finite NLL per temperature: "
@@ -318,27 +283,6 @@ def reliability_image(before, after, size=(640, 360)):
     return im
 
 
-def _batches(args, nc, dev):
-    """-> (images f32 [n,3,H,W], target u8 [n,H,W]) per batch, on the device."""
-    bs = args.batch_size
-    if args.synthetic:
-        from .dataset import ProceduralSeg
-        ds = ProceduralSeg(args.synthetic, args.height, args.width, nc, seed=12 + args.task, domain=args.task)
-        for i in range(0, len(ds), bs):
-            items = [ds[j] for j in range(i, min(i + bs, len(ds)))]
-            yield (torch.stack([im for im, _ in items]).to(dev),
-                   torch.stack([lab[0] for _, lab in items]).to(torch.uint8).to(dev))
-        return
-    from . import ops
-    from .dataset import open_dataset
-    ds = open_dataset(args.dataset, args.subset, args, augment=False)    # as evaluate.py opens it
-    for i in range(0, len(ds), bs):
-        items = [ds[j] for j in range(i, min(i + bs, len(ds)))]
-        img, lab, params = (torch.stack([it[k] for it in items]).to(dev) for k in range(3))
-        images, labels = ops.augment_batch(img, lab, params, nc)       # no flip, no shift; 255 -> nc - 1
-        yield images, labels[:, 0].to(torch.uint8).contiguous()
-
-
 class _Features:
     """The validation set as (features, target) batches on the device: kept up to ``budget`` bytes,
     beyond it the forward is run again on every sweep."""
@@ -355,7 +299,7 @@ class _Features:
             return
         kept, size, images = [], 0, 0
         with torch.no_grad():
-            for batch, target in _batches(self.args, self.nc, self.dev):
+            for _, batch, target in rc.batches(self.args, self.nc, self.dev):
                 feat = self.model.features(batch, self.args.task).contiguous()
                 images += batch.shape[0]
                 if kept is not None:
@@ -378,7 +322,7 @@ class _Features:
 
 def main(args):
     _refusals(args)
-    dev, nc, model = hc.load_model(args)
+    dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
     source = _Features(args, nc, dev, model, int(args.feature_cache_gb * 2 ** 30))
     base = source.meter([1.0], args.bins, 0).report()
     report = {"dataset": "synthetic" if args.synthetic else args.dataset, "task": args.task, "classes": nc,
@@ -410,21 +354,14 @@ def main(args):
         reliability_image(t1, scaled["temperatures"][0] if scaled else t1).save(path)
         report["written"] = [path]
         print(f"reliability diagram written to {path}")
-    with open(args.json, "w") as f:
-        json.dump(report, f, indent=1)
+    hc.write_json(report, args.json)
     return report
 
 
 def _refusals(args):
     """Raise a RuntimeError that names why this combination of flags is refused."""
-    if not 0 <= args.task < len(args.num_classes):
-        raise RuntimeError(f"--task {args.task}: the model has tasks 0 to {len(args.num_classes) - 1}")
-    if not args.synthetic and not args.dataset:
-        raise RuntimeError("give --dataset cityscapes|BDD|IDD or --synthetic N")
-    if args.synthetic and args.dataset:
-        raise RuntimeError("--dataset and --synthetic exclude each other")
-    if min(args.height, args.width, args.batch_size) < 1 or args.synthetic < 0:
-        raise RuntimeError("sizes and --batch-size must be positive")
+    rc.refuse_task(args.task, args.num_classes)
+    rc.refuse_data(args)
     if not 1 <= args.bins <= _calib_lib.MAX_BINS:
         raise RuntimeError(f"--bins must lie in [1, {_calib_lib.MAX_BINS}]")
     if args.fit and args.temperature:
@@ -440,17 +377,10 @@ def _refusals(args):
 
 
 def build_parser():
-    from .dataset import add_datadir_flags
     p = hc.RefusingParser(_refusals, description="calibration report: ECE, reliability and the fitted temperature")
     p.add_argument("--state", required=True, help="checkpoint of the model")
     p.add_argument("--num-classes", type=int, nargs="+", required=True)
     p.add_argument("--task", type=int, required=True, help="which task's decoder is calibrated")
-    p.add_argument("--dataset", choices=("cityscapes", "BDD", "IDD"))
-    p.add_argument("--subset", default="val")
-    p.add_argument("--synthetic", type=int, default=0, help="N procedural images instead of a dataset")
-    p.add_argument("--height", type=int, default=512, help="the network's input height")
-    p.add_argument("--width", type=int, default=1024, help="the network's input width")
-    p.add_argument("--batch-size", type=int, default=6)
     p.add_argument("--bins", type=int, default=15, help="equal-width confidence bins")
     p.add_argument("--temperature", type=float, nargs="+", help="also report at these temperatures")
     p.add_argument("--fit", action="store_true", help="fit the temperature that minimises the NLL and report at it")
@@ -459,7 +389,7 @@ def build_parser():
                    help="features kept on the device between sweeps; beyond it the forward runs again per sweep")
     p.add_argument("--json", required=True, help="write the report here")
     p.add_argument("--out", help="write reliability.png into this folder")
-    add_datadir_flags(p)
+    rc.add_data_flags(p)
     return p
 
 

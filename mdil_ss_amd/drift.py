@@ -18,15 +18,14 @@ per-class forgotten / gained rates.  ``--out`` writes ``<stem>_change.png`` (RGB
 applied to the change codes), ``<stem>_kl.png`` (L, ``round(255 min(kl, kl_max) / kl_max)``) and,
 with ``--labels``, ``<stem>_before_label.png`` and ``<stem>_after_label.png`` (train ids)."""
 import functools
-import json
 import os
-from argparse import Namespace
 
 import numpy as np
 import torch
 
 from . import _drift_lib
 from . import _head_common as hc
+from . import _report_common as rc
 from .fullres import ConfusionMeter
 
 _FN, _PATH = "drift_head", "drift"
@@ -77,13 +76,8 @@ def drift_head(feat_a, w_a, b_a, feat_b, w_b, b_b, *, target=None, ignore_index=
         raise RuntimeError(f"mdil {_FN}: feat_a on {dev}, feat_b on {feat_b.device}")
     N, H, W = feat_a.shape[0], feat_a.shape[1], feat_a.shape[2]
     hc.check_tables(_FN, _PATH, dev, torch.uint8, ((target, "target", (N, 2 * H, 2 * W)),))
-    if not -1 <= int(ignore_index) <= 255:
-        raise RuntimeError(f"mdil {_FN}: ignore_index {ignore_index} outside [-1, 255]")
-    c = dict(counters or {})
-    unknown = sorted(set(c) - set(_COUNTERS))
-    if unknown:
-        raise RuntimeError(f"mdil {_FN}: unknown counters {unknown} (known: {list(_COUNTERS)})")
-    c = {k: c.get(k) for k in _COUNTERS}
+    hc.check_ignore_index(_FN, ignore_index)
+    c = rc.check_counters(_FN, counters, _COUNTERS)
     hc.check_tables(_FN, _PATH, dev, torch.int64,
                     ((c["transition"], "transition", (nc, nc)), (c["confusion_a"], "confusion_a", (nc, nc)),
                      (c["confusion_b"], "confusion_b", (nc, nc)), (c["outcome"], "outcome", (nc, 4)),
@@ -91,16 +85,7 @@ def drift_head(feat_a, w_a, b_a, feat_b, w_b, b_b, *, target=None, ignore_index=
     hc.check_tables(_FN, _PATH, dev, torch.float64, ((c["sums"], "sums", (nc + 1,)),))
     if target is None and any(c[k] is not None for k in ("confusion_a", "confusion_b", "outcome")):
         raise RuntimeError(f"mdil {_FN}: confusion_a / confusion_b / outcome given without a target")
-    ws_bytes = 0
-    if c["sums"] is not None:
-        need = workspace_bytes(N, H, W, nc)
-        ws = c["workspace"]
-        if ws is None:
-            raise RuntimeError(f"mdil {_FN}: sums need a workspace (float64, {need} bytes) on the device")
-        _chk(ws, "workspace", torch.float64)
-        ws_bytes = ws.numel() * 8
-        if ws.device != dev or ws_bytes < need:
-            raise RuntimeError(f"mdil {_FN}: workspace must hold {need} bytes on {dev} (got {ws_bytes} on {ws.device})")
+    ws, ws_bytes = rc.check_workspace(_FN, _PATH, dev, c, lambda: workspace_bytes(N, H, W, nc))
     with torch.no_grad(), torch.cuda.device(dev):
         def new(want, dtype):
             return torch.empty(N, 2 * H, 2 * W, dtype=dtype, device=dev) if want else None
@@ -111,8 +96,7 @@ def drift_head(feat_a, w_a, b_a, feat_b, w_b, b_b, *, target=None, ignore_index=
                                 b_b.data_ptr(), N, H, W, nc, hc.ptr(target), int(ignore_index), hc.ptr(out["label_a"]),
                                 hc.ptr(out["label_b"]), hc.ptr(out["kl"]), hc.ptr(out["change"]),
                                 hc.ptr(c["transition"]), hc.ptr(c["confusion_a"]), hc.ptr(c["confusion_b"]),
-                                hc.ptr(c["outcome"]), hc.ptr(c["bad_targets"]), hc.ptr(c["sums"]),
-                                hc.ptr(c["workspace"]) if c["sums"] is not None else None, ws_bytes,
+                                hc.ptr(c["outcome"]), hc.ptr(c["bad_targets"]), hc.ptr(c["sums"]), ws, ws_bytes,
                                 torch.cuda.current_stream(dev).cuda_stream),
             "mdil_drift_head")
     return out
@@ -150,31 +134,15 @@ class DriftMeter:
                 self.tensors.update(confusion_a=z(nc, nc), confusion_b=z(nc, nc), outcome=z(nc, 4))
         elif scored != self.scored:
             raise RuntimeError("mdil DriftMeter.add: every call must come with a target, or none")
-        need = workspace_bytes(N, H, W, nc) // 8
-        ws = self.tensors.get("workspace")
-        if ws is None or ws.numel() < need:
-            self.tensors["workspace"] = torch.empty(need, dtype=torch.float64, device=dev)
+        rc.grow_workspace(self.tensors, workspace_bytes(N, H, W, nc), dev)
         return self.tensors
 
     def add(self, *source, target=None, **kw):
         """``add(model_a, model_b, images, task)`` or ``add(feat_a, w_a, b_a, feat_b, w_b, b_b)``,
         with ``target=t`` (u8 [N,2H,2W] train ids on the device) when scoring.  -> ``drift_head``'s dict."""
-        if isinstance(source[0], torch.nn.Module):
-            images = source[2]
-            if not isinstance(images, torch.Tensor) or images.dim() != 4:
-                raise RuntimeError("mdil DriftMeter.add: images must be a float32 [N,3,H,W] device tensor")
-            dev, N, H, W = images.device, images.shape[0], images.shape[2] // 2, images.shape[3] // 2
-            fn = compare
-        else:
-            feat = source[0]
-            _chk(feat, "feat_a")
-            if feat.dim() != 4:
-                raise RuntimeError("mdil DriftMeter.add: feat_a must be NHWC features [N,H,W,16]")
-            dev, (N, H, W) = feat.device, feat.shape[:3]
-            fn = drift_head
-        if dev.type != "cuda":
-            raise RuntimeError("mdil DriftMeter.add: inputs must be device tensors; there is no CPU fallback in the "
-                               "drift path")
+        if not isinstance(source[0], torch.nn.Module):
+            _chk(source[0], "feat_a")
+        fn, dev, N, H, W = rc.meter_source("DriftMeter", _PATH, source, 2, compare, drift_head, "feat_a")
         kw.update(target=target, ignore_index=self.ignore_index,
                   counters=self._counters(dev, target is not None, N, H, W))
         out = fn(*source, **kw)
@@ -187,10 +155,7 @@ class DriftMeter:
         if self.tensors is None:
             return {"transition": torch.zeros(self.nc, self.nc, dtype=torch.int64),
                     "sums": torch.zeros(self.nc + 1, dtype=torch.float64)}
-        bad = int(self.tensors["bad_targets"].item())
-        if bad:
-            raise RuntimeError(f"mdil DriftMeter: {bad} target pixels are outside [0, {self.nc}) and are not the "
-                               f"ignore index {self.ignore_index}")
+        rc.refuse_bad_targets("DriftMeter", self.tensors, self.nc, self.ignore_index)
         return {k: v.cpu() for k, v in self.tensors.items() if k not in ("workspace", "bad_targets")}
 
     def report(self, top=10):
@@ -267,40 +232,10 @@ def kl_bytes(kl, kl_max):
     return kl.clamp(max=kl_max).mul(255.0 / kl_max).round_().nan_to_num_(0.0).clamp_(0.0, 255.0).to(torch.uint8)
 
 
-def _batches(args, nc, dev):
-    """-> (stems, images f32 [n,3,H,W], target u8 [n,H,W] or None) per batch, on the device."""
-    bs = args.batch_size
-    if args.synthetic:
-        from .dataset import ProceduralSeg
-        ds = ProceduralSeg(args.synthetic, args.height, args.width, nc, seed=12 + args.task, domain=args.task)
-        for i in range(0, len(ds), bs):
-            items = [ds[j] for j in range(i, min(i + bs, len(ds)))]
-            target = torch.stack([lab[0] for _, lab in items]).to(torch.uint8).to(dev) if args.score else None
-            yield ([f"synthetic_{j:04d}" for j in range(i, i + len(items))],
-                   torch.stack([im for im, _ in items]).to(dev), target)
-        return
-    from . import ops
-    from .dataset import open_dataset
-    ds = open_dataset(args.dataset, args.subset, args, augment=False)    # as evaluate.py opens it
-    names = getattr(ds, "base", ds).filenames
-    stems = [os.path.splitext(os.path.basename(f))[0] for f in names]
-    if len(set(stems)) != len(stems):
-        raise RuntimeError(f"image names of {args.dataset} are not unique: the outputs would collide")
-    for i in range(0, len(ds), bs):
-        items = [ds[j] for j in range(i, min(i + bs, len(ds)))]
-        img, lab, params = (torch.stack([it[k] for it in items]).to(dev) for k in range(3))
-        images, labels = ops.augment_batch(img, lab, params, nc)       # no flip, no shift; 255 -> nc - 1
-        yield stems[i:i + len(items)], images, labels[:, 0].to(torch.uint8).contiguous() if args.score else None
-
-
-def _load(state, num_classes, task):
-    return hc.load_model(Namespace(state=state, num_classes=num_classes, task=task))
-
-
 def main(args):
     _refusals(args)
-    dev, nc, before = _load(args.before, args.before_num_classes, args.task)
-    _, _, after = _load(args.after, args.after_num_classes, args.task)
+    dev, nc, before = hc.load_model(args.before, args.before_num_classes, args.task)
+    _, _, after = hc.load_model(args.after, args.after_num_classes, args.task)
     reporting = args.report or args.score
     meter = DriftMeter(nc, nc - 1 if args.score else -1) if reporting else None
     if args.out:
@@ -308,7 +243,7 @@ def main(args):
     n_items = 0
     with hc.png_pool() as pool:
         png = hc.PngWriter(pool, args.out)
-        for stems, images, target in _batches(args, nc, dev):
+        for stems, images, target in rc.batches(args, nc, dev, score=args.score, unique_stems=True):
             n_items += len(stems)
             kw = dict(labels=bool(args.out and args.labels), kl=bool(args.out), change=bool(args.out))
             if meter is not None:
@@ -343,49 +278,31 @@ def main(args):
     if args.out:
         print(f"{len(png.written)} maps written to {args.out}")
     if args.json:
-        with open(args.json, "w") as f:
-            json.dump(report, f, indent=1)
+        hc.write_json(report, args.json)
     return report
 
 
 def _refusals(args):
     """Raise a RuntimeError that names why this combination of flags is refused."""
-    for name, classes in (("--before", args.before_num_classes), ("--after", args.after_num_classes)):
-        if not 0 <= args.task < len(classes):
-            raise RuntimeError(f"--task {args.task}: the {name} model has tasks 0 to {len(classes) - 1}")
-    ca, cb = args.before_num_classes[args.task], args.after_num_classes[args.task]
-    if ca != cb:
-        raise RuntimeError(f"--task {args.task}: {ca} classes before and {cb} after; the heads must agree")
+    rc.refuse_pair(args)
     if not args.report and not args.score and not args.out:
         raise RuntimeError("nothing to do: give --report, --score, --out DIR or several")
     if args.json and not args.report and not args.score:
         raise RuntimeError("--json writes the report: it needs --report or --score")
     if args.labels and not args.out:
         raise RuntimeError("--labels needs --out DIR")
-    if not args.synthetic and not args.dataset:
-        raise RuntimeError("give --dataset cityscapes|BDD|IDD or --synthetic N")
-    if args.synthetic and args.dataset:
-        raise RuntimeError("--dataset and --synthetic exclude each other")
-    if min(args.height, args.width, args.batch_size) < 1 or args.synthetic < 0:
-        raise RuntimeError("sizes and --batch-size must be positive")
+    rc.refuse_data(args)
     if not args.kl_max > 0:
         raise RuntimeError("--kl-max must be positive")
 
 
 def build_parser():
-    from .dataset import add_datadir_flags
     p = hc.RefusingParser(_refusals, description="drift report: two checkpoints compared on one task")
     p.add_argument("--before", required=True, help="checkpoint before the incremental step (the teacher)")
     p.add_argument("--before-num-classes", type=int, nargs="+", required=True)
     p.add_argument("--after", required=True, help="checkpoint after it (the student)")
     p.add_argument("--after-num-classes", type=int, nargs="+", required=True)
     p.add_argument("--task", type=int, required=True, help="which task's decoder is compared; both models have it")
-    p.add_argument("--dataset", choices=("cityscapes", "BDD", "IDD"))
-    p.add_argument("--subset", default="val")
-    p.add_argument("--synthetic", type=int, default=0, help="N procedural images instead of a dataset")
-    p.add_argument("--height", type=int, default=512, help="the network's input height")
-    p.add_argument("--width", type=int, default=1024, help="the network's input width")
-    p.add_argument("--batch-size", type=int, default=6)
     p.add_argument("--report", action="store_true", help="agreement, KL, KD loss and class transitions (no labels)")
     p.add_argument("--score", action="store_true", help="the report with the labels: mIoU before / after, "
                                                         "forgotten and gained rates")
@@ -393,7 +310,7 @@ def build_parser():
     p.add_argument("--out", help="write <stem>_change.png and <stem>_kl.png into this folder")
     p.add_argument("--kl-max", type=float, default=1.0, help="the KL divergence drawn as 255 in <stem>_kl.png")
     p.add_argument("--labels", action="store_true", help="also write <stem>_before_label.png and <stem>_after_label.png")
-    add_datadir_flags(p)
+    rc.add_data_flags(p)
     return p
 
 

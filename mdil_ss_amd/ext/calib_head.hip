@@ -40,7 +40,7 @@
 // added over the four lanes of a quad by two DPP steps (a fixed tree) and added by the quad's first
 // lane to its own fp64 slot in LDS, acc[wave][3k+j][quad].  After the loop lane 3k+j adds the 64
 // slots of its entry in (wave, quad) order and stores the total to the caller's workspace, one row
-// of 3 K doubles per work-group.  A second launch (3 K wavefronts) adds the rows -- lane l the rows
+// of 3 K doubles per work-group.  A second launch (head_common.h's fold_kernel, 3 K wavefronts) adds the rows -- lane l the rows
 // l, l + 64, ... ascending, then a fixed xor tree -- and adds the total to sums.  The grid is a
 // function of N * H * W, so the order is fixed by the shape and K.
 #include "../../include/mdil_calib.h"
@@ -110,13 +110,6 @@ __device__ __forceinline__ double dpp_f64(double v) {
 __device__ __forceinline__ double quad_sum(double v) {
   v += dpp_f64<0xb1>(v);
   v += dpp_f64<0x4e>(v);
-  return v;
-}
-
-// fold kernel's tree: a fixed order, the same on every run
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
   return v;
 }
 
@@ -339,27 +332,13 @@ __global__ __launch_bounds__(kWG, 2) void calib_head_kernel(const CalibArgs p) {
   }
 }
 
-// One wavefront per entry of sums: rows lane, lane + 64, ... ascending, then the tree.
-__global__ __launch_bounds__(64) void calib_fold_kernel(const double* __restrict__ workspace, int rows, int cols,
-                                                        double* __restrict__ sums) {
-  const int c = blockIdx.x;
-  double v = 0.0;
-  for (int b = threadIdx.x; b < rows; b += 64) v += workspace[(long long)b * cols + c];
-  v = wave_sum(v);
-  if (threadIdx.x == 0) sums[c] += v;
-}
-
-bool shape_ok(int N, int H, int W) {
-  return N > 0 && H > 0 && W > 0 && 2LL * W <= 0x7fffffffLL && (long long)N * H <= kMaxPixels / W;
-}
-
 }  // namespace
 
 API int mdil_calib_version(void) { return 100; }
 API const char* mdil_calib_last_error(void) { return g_err; }
 
 API long long mdil_calib_workspace_bytes(int N, int H, int W, int nc, int K) {
-  if (!shape_ok(N, H, W) || nc < MDIL_CALIB_MIN_CLASSES || nc > MDIL_CALIB_MAX_CLASSES || K < 1 ||
+  if (!shape_ok(N, H, W, kMaxPixels) || nc < MDIL_CALIB_MIN_CLASSES || nc > MDIL_CALIB_MAX_CLASSES || K < 1 ||
       K > MDIL_CALIB_MAX_TEMPS)
     return -1;
   return (long long)bounded_grid((long long)N * H * W, kWG, kMaxBlocks) * (3 * K) * (long long)sizeof(double);
@@ -376,7 +355,7 @@ API int mdil_calib_head(const float* x, const float* w, const float* bias, int N
     return MDIL_CALIB_ERR_INVALID;
   }
   if (!classes_ok(kFn, nc, MDIL_CALIB_MIN_CLASSES, MDIL_CALIB_MAX_CLASSES)) return MDIL_CALIB_ERR_INVALID;
-  if (!shape_ok(N, H, W)) {
+  if (!shape_ok(N, H, W, kMaxPixels)) {
     set_error("calib_head: too large (N %d, features %d x %d: at most 2^38 pixels, W below 2^30)", N, H, W);
     return MDIL_CALIB_ERR_INVALID;
   }
@@ -384,10 +363,7 @@ API int mdil_calib_head(const float* x, const float* w, const float* bias, int N
     set_error("calib_head: a target is required");
     return MDIL_CALIB_ERR_INVALID;
   }
-  if (ignore_index < -1 || ignore_index > 255) {
-    set_error("calib_head: ignore_index=%d outside [-1, 255]", ignore_index);
-    return MDIL_CALIB_ERR_INVALID;
-  }
+  if (!ignore_ok(kFn, ignore_index)) return MDIL_CALIB_ERR_INVALID;
   if (K < 1 || K > MDIL_CALIB_MAX_TEMPS || !temps) {
     set_error("calib_head: K=%d outside [1, %d] or temps NULL (%p; a HOST pointer)", K, MDIL_CALIB_MAX_TEMPS,
               (const void*)temps);
@@ -421,11 +397,7 @@ API int mdil_calib_head(const float* x, const float* w, const float* bias, int N
   const long long npix = (long long)N * H * W;
   const int grid = bounded_grid(npix, kWG, kMaxBlocks);
   const long long need = (long long)grid * (3 * K) * (long long)sizeof(double);
-  if (sums && (!workspace || workspace_bytes < need)) {
-    set_error("calib_head: sums need a workspace of %lld bytes (got %p, %lld bytes)", need, workspace,
-              workspace_bytes);
-    return MDIL_CALIB_ERR_INVALID;
-  }
+  if (!workspace_ok(kFn, sums, workspace, workspace_bytes, need)) return MDIL_CALIB_ERR_INVALID;
   CalibArgs p;
   p.x = x, p.w = w, p.bias = bias;
   p.npix = npix, p.plane = 4 * npix;
@@ -444,7 +416,7 @@ API int mdil_calib_head(const float* x, const float* w, const float* bias, int N
   hipLaunchKernelGGL(calib_head_kernel, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, p);
   if (!launched(kFn)) return MDIL_CALIB_ERR_LAUNCH;
   if (sums) {
-    hipLaunchKernelGGL(calib_fold_kernel, dim3(3 * K), dim3(64), 0, (hipStream_t)stream, p.workspace, grid, 3 * K,
+    hipLaunchKernelGGL(fold_kernel<>, dim3(3 * K), dim3(64), 0, (hipStream_t)stream, p.workspace, grid, 3 * K,
                        sums);
     if (!launched(kFn)) return MDIL_CALIB_ERR_LAUNCH;
   }

@@ -32,9 +32,9 @@
 // the wave by a fixed xor-shuffle tree, and added by lane 0 to the wave's own fp64 slot in LDS.
 // sums[nc]: a lane adds its kd values to an fp64 register (pixel order over its trips); one tree
 // at the end.  After the loop the four waves' slots are added in wave order and stored to the
-// caller's workspace, one row of nc + 1 doubles per work-group.  A second launch (nc + 1
-// wavefronts) adds the rows -- lane l the rows l, l + 64, ... ascending, then the same tree -- and
-// adds the total to sums[c].  The grid is a function of N * H * W, so the order is fixed by the shape.
+// caller's workspace, one row of nc + 1 doubles per work-group.  A second launch (head_common.h's
+// fold_kernel, nc + 1 wavefronts) adds the rows -- lane l the rows l, l + 64, ... ascending, then
+// the same tree -- and adds the total to sums[c].  The grid is a function of N * H * W, so the order is fixed by the shape.
 #include "../../include/mdil_drift.h"
 #include "head_common.h"
 
@@ -60,27 +60,6 @@ struct DriftArgs {
   unsigned long long *transition, *confusion_a, *confusion_b, *outcome, *bad_targets;
   double* workspace;                                 // NULL without sums
 };
-
-// the four logits (a*2+b) of class c for one feature pixel: bias first, then ci ascending
-// (predict_head.hip's chain)
-__device__ __forceinline__ f32x4 logits4(const f32x4 (&xv)[4], const float (*Wc)[4], float b) {
-  f32x4 acc = {b, b, b, b};
-#pragma unroll
-  for (int ci = 0; ci < 16; ++ci) {
-    const f32x4 wv = *reinterpret_cast<const f32x4*>(Wc[ci]);
-    const float xs = xv[ci >> 2][ci & 3];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(xs, wv[k], acc[k]);
-  }
-  return acc;
-}
-
-// Sum over the 64 lanes of a wave, every lane active: a fixed tree, the same on every run.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 __device__ __forceinline__ void flush(uint32_t* hist, unsigned long long* out, int n) {
   if (!out) return;
@@ -271,27 +250,13 @@ __global__ __launch_bounds__(kWG, 2) void drift_head_kernel(const DriftArgs p) {
   }
 }
 
-// One wavefront per entry of sums: rows lane, lane + 64, ... ascending, then the tree.
-__global__ __launch_bounds__(64) void drift_fold_kernel(const double* __restrict__ workspace, int rows,
-                                                        int nc, double* __restrict__ sums) {
-  const int c = blockIdx.x;
-  double v = 0.0;
-  for (int b = threadIdx.x; b < rows; b += 64) v += workspace[(long long)b * (nc + 1) + c];
-  v = wave_sum(v);
-  if (threadIdx.x == 0) sums[c] += v;
-}
-
-bool shape_ok(int N, int H, int W) {
-  return N > 0 && H > 0 && W > 0 && 2LL * W <= 0x7fffffffLL && (long long)N * H <= kMaxPixels / W;
-}
-
 }  // namespace
 
 API int mdil_drift_version(void) { return 100; }
 API const char* mdil_drift_last_error(void) { return g_err; }
 
 API long long mdil_drift_workspace_bytes(int N, int H, int W, int nc) {
-  if (!shape_ok(N, H, W) || nc < MDIL_DRIFT_MIN_CLASSES || nc > MDIL_DRIFT_MAX_CLASSES) return -1;
+  if (!shape_ok(N, H, W, kMaxPixels) || nc < MDIL_DRIFT_MIN_CLASSES || nc > MDIL_DRIFT_MAX_CLASSES) return -1;
   return (long long)bounded_grid((long long)N * H * W, kWG, kMaxBlocks) * (nc + 1) * (long long)sizeof(double);
 }
 
@@ -307,14 +272,11 @@ API int mdil_drift_head(const float* xa, const float* wa, const float* ba, const
     return MDIL_DRIFT_ERR_INVALID;
   }
   if (!classes_ok(kFn, nc, MDIL_DRIFT_MIN_CLASSES, MDIL_DRIFT_MAX_CLASSES)) return MDIL_DRIFT_ERR_INVALID;
-  if (!shape_ok(N, H, W)) {
+  if (!shape_ok(N, H, W, kMaxPixels)) {
     set_error("drift_head: too large (N %d, features %d x %d: at most 2^38 pixels, W below 2^30)", N, H, W);
     return MDIL_DRIFT_ERR_INVALID;
   }
-  if (ignore_index < -1 || ignore_index > 255) {
-    set_error("drift_head: ignore_index=%d outside [-1, 255]", ignore_index);
-    return MDIL_DRIFT_ERR_INVALID;
-  }
+  if (!ignore_ok(kFn, ignore_index)) return MDIL_DRIFT_ERR_INVALID;
   if (!target && (confusion_a || confusion_b || outcome)) {
     set_error("drift_head: confusion_a, confusion_b and outcome need a target");
     return MDIL_DRIFT_ERR_INVALID;
@@ -331,11 +293,7 @@ API int mdil_drift_head(const float* xa, const float* wa, const float* ba, const
   const long long npix = (long long)N * H * W;
   const int grid = bounded_grid(npix, kWG, kMaxBlocks);
   const long long need = (long long)grid * (nc + 1) * (long long)sizeof(double);
-  if (sums && (!workspace || workspace_bytes < need)) {
-    set_error("drift_head: sums need a workspace of %lld bytes (got %p, %lld bytes)", need, workspace,
-              workspace_bytes);
-    return MDIL_DRIFT_ERR_INVALID;
-  }
+  if (!workspace_ok(kFn, sums, workspace, workspace_bytes, need)) return MDIL_DRIFT_ERR_INVALID;
   DriftArgs p;
   p.xa = xa, p.wa = wa, p.ba = ba, p.xb = xb, p.wb = wb, p.bb = bb;
   p.npix = npix, p.W = W, p.nc = nc;
@@ -350,7 +308,7 @@ API int mdil_drift_head(const float* xa, const float* wa, const float* ba, const
   hipLaunchKernelGGL(drift_head_kernel, dim3(grid), dim3(kWG), 0, (hipStream_t)stream, p);
   if (!launched(kFn)) return MDIL_DRIFT_ERR_LAUNCH;
   if (sums) {
-    hipLaunchKernelGGL(drift_fold_kernel, dim3(nc + 1), dim3(64), 0, (hipStream_t)stream, p.workspace, grid, nc,
+    hipLaunchKernelGGL(fold_kernel<>, dim3(nc + 1), dim3(64), 0, (hipStream_t)stream, p.workspace, grid, nc + 1,
                        sums);
     if (!launched(kFn)) return MDIL_DRIFT_ERR_LAUNCH;
   }

@@ -1,8 +1,16 @@
-// What predict_head.hip, fullres_head.hip and ensemble_head.hip share, written once.  Private to
-// mdil_ss_amd/ext (not under include/): it is compiled INTO each of the three libraries, which stay
-// self-contained binaries -- the error buffer below is one per library -- and it shares nothing
-// with csrc/.  The arithmetic contracts (order of operations, roundings) are documented in the
-// three kernels' header comments; the helpers here are the single spelling of the steps they name.
+// What the five head add-ons share, written once.  Private to mdil_ss_amd/ext (not under include/):
+// it is compiled INTO each of the five libraries, which stay self-contained binaries -- the error
+// buffer below is one per library -- and it shares nothing with csrc/, similarity.hip or tsne.hip.
+// The arithmetic contracts (order of operations, roundings) are documented in the kernels' header
+// comments; the helpers here are the single spelling of the steps they name.  Who uses what:
+//   every head      set_error, bounded_grid, launched, classes_ok
+//   predict         vote, stage_head, logits4, colour_ok
+//   fullres         axis, gather, stage_head, confusion_zero, out_size_ok, colour_ok, scoring_ok
+//   ensemble        vote, axis, gather, confusion_zero, out_size_ok, colour_ok, scoring_ok
+//   drift           vote, stage_head, logits4, confusion_zero, wave_sum, fold_kernel, shape_ok, ignore_ok, workspace_ok
+//   calib           vote, fold_kernel (and through it wave_sum), shape_ok, ignore_ok, workspace_ok
+// calib_head.hip forms its logits per parity from its own Wp[a*2+b][c][ci] staging, not through
+// logits4 (another LDS layout, the same chain), and keeps its DPP sums.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -87,6 +95,21 @@ __device__ __forceinline__ void vote(int c, float u, float& best, int& bi) {
   bi = t ? c : bi;
 }
 
+// The four logits (a*2+b) of class c for one feature pixel: bias first, then ci ascending.  Wc is
+// Wl[c] of stage_head's table.  predict_head.hip and drift_head.hip walk the classes with it: one
+// chain, so drift's labels are predict's labels bit for bit.
+__device__ __forceinline__ f32x4 logits4(const f32x4 (&xv)[4], const float (*Wc)[4], float b) {
+  f32x4 acc = {b, b, b, b};
+#pragma unroll
+  for (int ci = 0; ci < 16; ++ci) {
+    const f32x4 wv = *reinterpret_cast<const f32x4*>(Wc[ci]);
+    const float xs = xv[ci >> 2][ci & 3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(xs, wv[k], acc[k]);
+  }
+  return acc;
+}
+
 // Stages the head's tables into LDS, by a work-group of WG lanes (the caller's barrier follows):
 //   Wl[c][ci][a*2+b] = W[ci][c][a][b];  Bl[c] = bias[c];
 //   Pl[c] = r | g << 8 | b << 16 of the palette (0 without a `colour` map);
@@ -119,6 +142,27 @@ template <int WG, int N>
 __device__ __forceinline__ void confusion_zero(uint32_t (&hist)[N], uint32_t& bad, int nc) {
   for (int i = threadIdx.x; i < nc * nc; i += WG) hist[i] = 0u;
   if (threadIdx.x == 0) bad = 0u;
+}
+
+// Sum over the 64 lanes of a wave, every lane active: a fixed xor-shuffle tree, the same on every run.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// The second launch of drift_head and calib_head: sums[c] += the column c of the `rows` x `cols`
+// workspace, one row per work-group of the main kernel.  One wavefront per entry of sums: lane l
+// adds the rows l, l + 64, ... ascending, then the tree.  A template only so that the three
+// libraries that never launch it do not carry it.
+template <int LANES = 64>
+__global__ __launch_bounds__(LANES) void fold_kernel(const double* __restrict__ workspace, int rows, int cols,
+                                                     double* __restrict__ sums) {
+  const int c = blockIdx.x;
+  double v = 0.0;
+  for (int b = threadIdx.x; b < rows; b += LANES) v += workspace[(long long)b * cols + c];
+  v = wave_sum(v);
+  if (threadIdx.x == 0) sums[c] += v;
 }
 
 // -------------------------------------------------------------------------------------- host
@@ -155,17 +199,33 @@ inline bool colour_ok(const char* fn, const void* colour, const void* palette) {
   return false;
 }
 
+inline bool ignore_ok(const char* fn, int ignore_index) {
+  if (ignore_index >= -1 && ignore_index <= 255) return true;
+  set_error("%s: ignore_index=%d outside [-1, 255]", fn, ignore_index);
+  return false;
+}
+
 inline bool scoring_ok(const char* fn, const void* target, const void* confusion, const void* bad_targets,
                        int ignore_index) {
   if (target && (!confusion || !bad_targets)) {
     set_error("%s: a target needs a confusion matrix and a bad_targets counter", fn);
     return false;
   }
-  if (ignore_index < -1 || ignore_index > 255) {
-    set_error("%s: ignore_index=%d outside [-1, 255]", fn, ignore_index);
-    return false;
-  }
-  return true;
+  return ignore_ok(fn, ignore_index);
+}
+
+// Features [N,H,W,16] the grid-stride kernels can index: at most max_pixels of them, 2 W in an int.
+// Sets no message: the callers word their own.
+inline bool shape_ok(int N, int H, int W, long long max_pixels) {
+  return N > 0 && H > 0 && W > 0 && 2LL * W <= 0x7fffffffLL && (long long)N * H <= max_pixels / W;
+}
+
+// `sums` come with a workspace of at least `need` bytes (one row per work-group of the main kernel).
+inline bool workspace_ok(const char* fn, const void* sums, const void* workspace, long long workspace_bytes,
+                         long long need) {
+  if (!sums || (workspace && workspace_bytes >= need)) return true;
+  set_error("%s: sums need a workspace of %lld bytes (got %p, %lld bytes)", fn, need, workspace, workspace_bytes);
+  return false;
 }
 
 }  // namespace

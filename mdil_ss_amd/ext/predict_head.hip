@@ -28,19 +28,6 @@ constexpr int kMaxC = MDIL_PREDICT_MAX_CLASSES;
 constexpr int kMaxBlocks = 2048;                     // beyond 524,288 feature pixels the loop strides
 constexpr char kFn[] = "predict_head";
 
-// the four logits (a*2+b) of class c for one feature pixel: bias first, then ci ascending
-__device__ __forceinline__ f32x4 logits4(const f32x4 (&xv)[4], const float (*Wc)[4], float b) {
-  f32x4 acc = {b, b, b, b};
-#pragma unroll
-  for (int ci = 0; ci < 16; ++ci) {
-    const f32x4 wv = *reinterpret_cast<const f32x4*>(Wc[ci]);
-    const float xs = xv[ci >> 2][ci & 3];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] = __builtin_fmaf(xs, wv[k], acc[k]);
-  }
-  return acc;
-}
-
 __global__ __launch_bounds__(kWG) void predict_head_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
     long long npix, int W, int nc, const unsigned char* __restrict__ palette,

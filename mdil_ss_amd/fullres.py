@@ -194,7 +194,7 @@ def _runs(shapes):
 
 def main(args):
     _refusals(args)
-    dev, nc, model = hc.load_model(args)
+    dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
     id_map = load_label_ids(args.label_ids, nc).to(dev) if args.label_ids else None
     palette = default_palette(nc).contiguous().to(dev) if args.colour else None
     meter = ConfusionMeter(nc, nc - 1) if args.score else None

@@ -314,7 +314,7 @@ def positions(args):
 
 def main(args):
     _refusals(args)
-    dev, nc, model = hc.load_model(args)
+    dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
     stem, images, label = _sample(args, nc, dev)
     feat = latents(model, images, args.task, args.layer)
     h, w, C = feat.shape[1:]

@@ -110,7 +110,7 @@ def _batches(args, nc, pool, dev):
 
 
 def main(args):
-    dev, nc, model = hc.load_model(args)
+    dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
     palette = None
     if args.colour:
         if args.palette:

@@ -21,13 +21,13 @@ centroid shift.
 per layer: the Frechet distance between the two domains' features and, when both tasks have the
 same class count, the distance between their per-class centroids.  Rows labelled with the task's
 last (ignore) class are left out of every moment."""
-import json
 from argparse import Namespace
 
 import numpy as np
 import torch
 
 from . import _head_common as hc
+from . import _report_common as rc
 from . import _similarity_lib
 from . import latent
 
@@ -304,9 +304,9 @@ def _lists(c):
 
 
 def _side_args(args, task, dataset, datadir):
-    """The namespace drift's batching reads, for one side."""
+    """The namespace the batch feeder reads, for one side."""
     ns = Namespace(**vars(args))
-    ns.task, ns.dataset, ns.score = task, dataset, True
+    ns.task, ns.dataset = task, dataset
     if dataset and datadir:
         from .dataset import _ALIASES
         setattr(ns, {"cityscapes": "cs_datadir", "BDD": "bdd_datadir", "IDD": "idd_datadir"}[_ALIASES[dataset]], datadir)
@@ -315,9 +315,8 @@ def _side_args(args, task, dataset, datadir):
 
 def _feed(args, nc, dev, layers, each):
     """Runs ``each(layer, images, target)`` over every batch and layer; -> the number of images."""
-    from .drift import _batches
     seen = 0
-    for stems, images, target in _batches(args, nc, dev):
+    for stems, images, target in rc.batches(args, nc, dev, unique_stems=True):
         seen += len(stems)
         for layer in layers:
             each(layer, images, target)
@@ -325,9 +324,8 @@ def _feed(args, nc, dev, layers, each):
 
 
 def _checkpoints(args):
-    from .drift import _load
-    dev, nc, before = _load(args.before, args.before_num_classes, args.task)
-    _, _, after = _load(args.after, args.after_num_classes, args.task)
+    dev, nc, before = hc.load_model(args.before, args.before_num_classes, args.task)
+    _, _, after = hc.load_model(args.after, args.after_num_classes, args.task)
     meters = {}
 
     def each(layer, images, target):
@@ -354,7 +352,7 @@ def _checkpoints(args):
 
 
 def _domains(args):
-    dev, _, model = hc.load_model(Namespace(state=args.state, num_classes=args.num_classes, task=args.task_a))
+    dev, _, model = hc.load_model(args.state, args.num_classes, args.task_a)
     sides = {}
     for key, task, dataset, datadir in (("a", args.task_a, args.dataset_a, args.datadir_a),
                                         ("b", args.task_b, args.dataset_b, args.datadir_b)):
@@ -396,8 +394,7 @@ def main(args):
     _refusals(args)
     report = _checkpoints(args) if args.before else _domains(args)
     if args.json:
-        with open(args.json, "w") as f:
-            json.dump(report, f, indent=1)
+        hc.write_json(report, args.json)
     return report
 
 
@@ -418,12 +415,7 @@ def _refusals(args):
             raise RuntimeError("--before, --before-num-classes, --after and --after-num-classes go together")
         if args.task is None:
             raise RuntimeError("--before / --after need --task T")
-        for name, classes in (("--before", args.before_num_classes), ("--after", args.after_num_classes)):
-            if not 0 <= args.task < len(classes):
-                raise RuntimeError(f"--task {args.task}: the {name} model has tasks 0 to {len(classes) - 1}")
-        ca, cb = args.before_num_classes[args.task], args.after_num_classes[args.task]
-        if ca != cb:
-            raise RuntimeError(f"--task {args.task}: {ca} classes before and {cb} after; the heads must agree")
+        ca = rc.refuse_pair(args)
         if bool(args.synthetic) == bool(args.dataset):
             raise RuntimeError("give exactly one of --dataset cityscapes|BDD|IDD and --synthetic N")
         counts = [ca]
@@ -447,7 +439,6 @@ def _refusals(args):
 
 
 def build_parser():
-    from .dataset import add_datadir_flags
     names = ("cityscapes", "BDD", "IDD")
     p = hc.RefusingParser(_refusals, description="representation similarity: two checkpoints on one task, or two "
                                                  "domains through one checkpoint")
@@ -456,7 +447,6 @@ def build_parser():
     p.add_argument("--after", help="checkpoint after it")
     p.add_argument("--after-num-classes", type=int, nargs="+")
     p.add_argument("--task", type=int, help="--before / --after: which task's adapters and decoder run")
-    p.add_argument("--dataset", choices=names, help="--before / --after: the validation set")
     p.add_argument("--state", help="one checkpoint, two domains")
     p.add_argument("--num-classes", type=int, nargs="+")
     p.add_argument("--task-a", type=int)
@@ -465,14 +455,10 @@ def build_parser():
     p.add_argument("--task-b", type=int)
     p.add_argument("--dataset-b", choices=names)
     p.add_argument("--datadir-b", help="root folder of --dataset-b")
-    p.add_argument("--synthetic", type=int, default=0, help="N procedural images (per domain) instead of datasets")
     p.add_argument("--layers", nargs="+", choices=LAYERS, default=list(LAYERS))
-    p.add_argument("--subset", default="val")
-    p.add_argument("--height", type=int, default=512, help="the network's input height")
-    p.add_argument("--width", type=int, default=1024, help="the network's input width")
-    p.add_argument("--batch-size", type=int, default=6)
     p.add_argument("--json", help="write the report (with its matrices) here")
-    add_datadir_flags(p)
+    rc.add_data_flags(p, "--before / --after: the validation set",
+                      "N procedural images (per domain) instead of datasets")
     return p
 
 

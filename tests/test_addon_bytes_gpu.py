@@ -1,7 +1,8 @@
-"""GPU: the three inference add-ons write the bytes they wrote before they came to share
-mdil_ss_amd/ext/head_common.h.  Every output buffer (label, colour, confidence as raw float bytes,
-confusion, bad-target count) of the cases in tests/addon_bytes_cases.py is compared, as a SHA-256,
-with tests/golden/addon_bytes.json, recorded on an MI355X from the unshared kernel sources.
+"""GPU: the three inference add-ons and the two report add-ons (drift, calib) write the bytes they
+wrote before they came to share mdil_ss_amd/ext/head_common.h.  Every output buffer (label, colour,
+confidence as raw float bytes, confusion, bad-target count; of drift and calib every map, counter
+and fp64 sum, of their meters the report) of the cases in tests/addon_bytes_cases.py is compared, as
+a SHA-256, with tests/golden/addon_bytes.json, recorded on an MI355X from the unshared kernel sources.
 Equality is exact: there is no tolerance."""
 import json
 
