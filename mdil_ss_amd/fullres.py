@@ -116,13 +116,20 @@ class ConfusionMeter:
         """-> (mean, per_class) in float64: tp = diagonal, fp = column sum - tp, fn = row sum - tp,
         tp / (tp + fp + fn + 1e-15); the ignore class is left out of the classes and of the mean."""
         m = (self.matrix() if matrix is None else matrix).double()
-        k = self.nc - 1 if 0 <= self.ignore_index < self.nc else self.nc
-        if 0 <= self.ignore_index < self.nc - 1:
-            raise RuntimeError("mdil ConfusionMeter: the ignore class must be the last one (iouEval's rule)")
-        tp = m.diagonal()
-        fp, fn = m.sum(0) - tp, m.sum(1) - tp
-        iou = (tp / (tp + fp + fn + 1e-15))[:k]
-        return iou.mean(), iou
+        return iou_rule(self.nc, self.ignore_index, m.diagonal(), m.sum(0), m.sum(1))
+
+
+def iou_rule(nc, ignore_index, both, predicted, labelled):
+    """The ``iouEval`` rule on per-class float64 counts [nc]: ``both`` pixels in the intersection,
+    ``predicted`` and ``labelled`` in each of the two sets -> (mean, per_class) of
+    both / (union + 1e-15); the ignore class is left out of the classes and of the mean.
+    ``ConfusionMeter.iou`` and ``boundary.BoundaryMeter`` score with it."""
+    k = nc - 1 if 0 <= ignore_index < nc else nc
+    if 0 <= ignore_index < nc - 1:
+        raise RuntimeError("mdil ConfusionMeter: the ignore class must be the last one (iouEval's rule)")
+    fp, fn = predicted - both, labelled - both
+    iou = (both / (both + fp + fn + 1e-15))[:k]
+    return iou.mean(), iou
 
 
 # ------------------------------------------------------------------------------------------ CLI
@@ -249,10 +256,12 @@ def _refusals(args):
         raise RuntimeError("sizes and --batch-size must be positive")
 
 
-def add_flags(p, at_scale_1=""):
-    """The flags of this command line, which ``python -m mdil_ss_amd.ensemble`` shares."""
+def add_flags(p, at_scale_1="", maps=True):
+    """The flags of this command line, which ``python -m mdil_ss_amd.ensemble`` shares;
+    ``maps=False``: those of ``python -m mdil_ss_amd.boundary``, which writes no label or colour map
+    and can score maps already written instead of running a checkpoint."""
     from .dataset import add_datadir_flags
-    p.add_argument("--state", required=True, help="checkpoint written by the trainers (or by the reference)")
+    p.add_argument("--state", required=maps, help="checkpoint written by the trainers (or by the reference)")
     p.add_argument("--num-classes", type=int, nargs="+", required=True)
     p.add_argument("--task", type=int, required=True, help="which task's decoder predicts")
     p.add_argument("--dataset", choices=("cityscapes", "BDD", "IDD"))
@@ -265,10 +274,12 @@ def add_flags(p, at_scale_1=""):
     p.add_argument("--batch-size", type=int, default=6)
     p.add_argument("--score", action="store_true", help="mIoU and per-class IoU against the full-size labels")
     p.add_argument("--json", help="write the score (with the confusion matrix) here")
-    p.add_argument("--out", help="write <stem>_label.png at the image's own size into this folder")
-    p.add_argument("--colour", action="store_true", help="also write <stem>_colour.png")
-    p.add_argument("--label-ids", help=f"label PNGs in the dataset's own ids: one of {sorted(LABEL_IDS)} or a "
-                                       "JSON file with one id per class (default: train ids)")
+    p.add_argument("--out", help="write <stem>_label.png at the image's own size into this folder" if maps else
+                   "write <stem>_boundary.png at the image's own size into this folder")
+    if maps:
+        p.add_argument("--colour", action="store_true", help="also write <stem>_colour.png")
+        p.add_argument("--label-ids", help=f"label PNGs in the dataset's own ids: one of {sorted(LABEL_IDS)} or a "
+                                           "JSON file with one id per class (default: train ids)")
     add_datadir_flags(p)
     return p
 
