@@ -1,6 +1,6 @@
 """The fp64 reference of the calibration tests (tests/test_calib_cpu.py, tests/test_calib_gpu.py),
 straight from logits and targets: softmax, equal-width confidence bins and the textbook ECE, MCE,
-NLL, Brier score and entropy.  Also the tests' inputs: the draw of tests/test_predict_gpu.py and
+NLL, Brier score and entropy.  Also the tests' inputs: ``head_inputs`` of tests/head_cases.py and
 targets sampled from the softmax of the fp64 logits at temperature 1.7, salted with ignored and
 out-of-range pixels.  Nothing here touches a device."""
 import functools
@@ -8,29 +8,11 @@ import functools
 import torch
 import torch.nn.functional as F
 
+from tests.head_cases import CLASSES, SHAPES, U, head64, head_inputs  # noqa: F401  (the constants: for the suites)
+
 Q_ONE = 1 << 24
-U = 2.0 ** -24
-CLASSES = (2, 20, 27, 32)
-SHAPES = ((1, 1, 1), (1, 9, 7), (2, 12, 20), (3, 16, 48))
 T_TARGETS = 1.7                                   # the temperature the targets are sampled at
 OUT_OF_RANGE = 200
-
-
-def draw(nc, shape, seed):
-    """tests/test_predict_gpu.py::case's draw -> x [N,16,H,W], w [16,nc,2,2], b [nc]."""
-    N, H, W = shape
-    g = torch.Generator().manual_seed(seed)
-    w = torch.randn(16, nc, 2, 2, generator=g) * 0.3
-    b = torch.randn(nc, generator=g) * 0.2
-    x = F.relu(torch.randn(N, 16, H, W, generator=g))
-    return x, w, b
-
-
-def logits64(x, w, b):
-    """-> (fp64 logits [N,nc,2H,2W], S = max_c (|b| + sum |x||w|) [N,2H,2W])."""
-    logits = F.conv_transpose2d(x.double(), w.double(), b.double(), stride=2)
-    S = F.conv_transpose2d(x.double().abs(), w.double().abs(), b.double().abs(), stride=2)
-    return logits, S.max(1)[0]
 
 
 def sample_targets(logits, nc, seed, ignore, t0=T_TARGETS, salt=True):
@@ -49,10 +31,12 @@ def sample_targets(logits, nc, seed, ignore, t0=T_TARGETS, salt=True):
 
 @functools.lru_cache(maxsize=None)
 def case(nc, shape, ignore_last):
-    """-> dict of a test case, computed once and never modified: x, w, b, fp64 ``logits``, ``S``,
-    ``target`` (u8), ``ignore``, ``counted`` mask, ``bad`` (pixels out of range)."""
-    x, w, b = draw(nc, shape, 10 * nc + shape[1])
-    logits, S = logits64(x, w, b)
+    """-> dict of a test case, computed once and never modified: x, w, b, fp64 ``logits``,
+    ``S`` = max_c (|b| + sum |x||w|) [N,2H,2W], ``target`` (u8), ``ignore``, ``counted`` mask, ``bad``
+    (pixels out of range)."""
+    x, w, b = head_inputs(nc, shape)
+    logits, S = head64(x, w, b)
+    S = S.max(1)[0]
     ignore = nc - 1 if ignore_last else 255
     target = sample_targets(logits, nc, 7 * nc + shape[2], ignore)
     tl = target.long()

@@ -17,10 +17,10 @@ import re
 import torch
 import torch.nn.functional as F
 
+from tests.head_cases import CLASSES, U, cap, gamma  # noqa: F401  (CLASSES and cap are for the two suites)
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -24
 K_MAX, CS_MAX = 96, 64
-CLASSES = (2, 20, 27, 32)
 MODES = ("prob", "logit")
 # view shapes (N, H, W), mirrored flags, output size
 CASES = [
@@ -36,10 +36,6 @@ CASES = [
 # goes round the kernel's bounded grid a second time (nc = 2 only)
 BIG = ([(1, 200, 300), (1, 150, 225)], [0, 1], (1025, 2051))
 BIG_NC, BIG_SEED = 2, 2099
-
-
-def gamma(k):
-    return k * U / (1 - k * U)
 
 
 def header_constants():
@@ -95,16 +91,3 @@ def case(nc, index, mode):
     xs, w, b = case_inputs(nc, index)
     k, cs = header_constants()
     return (xs, w, b, flips, size) + reference(xs, w, b, flips, size, mode, k, cs)
-
-
-def cap(pixels):
-    return 0 if pixels < 100 else max(1, pixels // 1000)
-
-
-def check_labels(label, ref, excluded, what):
-    n_ex = int(excluded.sum())
-    print(f"{what}: excluded {n_ex} of {excluded.numel()} pixels (cap {cap(excluded.numel())})")
-    assert n_ex <= cap(excluded.numel()), f"{what}: {n_ex} pixels are fp32 near-ties"
-    assert label.dtype == torch.uint8 and tuple(label.shape) == tuple(ref.shape)
-    wrong = (label.long() != ref) & ~excluded
-    assert not wrong.any(), f"{what}: {int(wrong.sum())} of {wrong.numel()} labels differ from the fp64 argmax"

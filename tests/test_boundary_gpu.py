@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import boundary_reference as R
+from tests import head_cases as HC
 
 pytestmark = pytest.mark.gpu
 
@@ -22,9 +23,7 @@ ALL8 = (1, 2, 4, 8, 16, 32, 64, 128)
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "the boundary path needs an MI355X"
-    import mdil_ss_amd  # noqa: F401
-    return torch.device("cuda", 0)
+    return HC.device("boundary")
 
 
 def perturbed(target, n_labels, seed, shift=2, share=0.01):
@@ -188,10 +187,7 @@ def test_images_of_a_batch_never_see_each_other(dev):
 
 def test_side_stream_gives_the_same(dev):
     p, t, nc, widths, ign, dp, dt, want = case("procedural 27")
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        got_p, got_t, got = run(dev, p, t, nc, widths, ign)
-    side.synchronize()
+    got_p, got_t, got = HC.side_stream(lambda: run(dev, p, t, nc, widths, ign))
     assert np.array_equal(got_p, dp) and np.array_equal(got_t, dt)
     check_counters(got, want)
 
@@ -204,38 +200,30 @@ def test_guard_bands_and_the_workspace_bound(dev):
     lib = _boundary_lib.load()
     p, t, nc, widths, ign, dp, dt, want = case("odd width, two images")
     N, H, W = p.shape
-    npx, G = p.size, 256
+    npx = p.size
     need = lib.mdil_boundary_workspace_bytes(N, H, W)
-    off_p = G
-    off_t = (off_p + npx + G + 15) // 16 * 16
-    off_w = (off_t + npx + G + 15) // 16 * 16
-    total = off_w + need + G
-    arena = torch.full((total,), 0xA5, dtype=torch.uint8, device=dev)
+    arena = HC.Arena(dev, {"dist_pred": npx, "dist_target": npx, "workspace": need})
     counters = B.new_counters(nc, len(widths) + 1, dev)
     pd, td = torch.from_numpy(p).to(dev), torch.from_numpy(t).to(dev)
     import ctypes as C
-    base = arena.data_ptr()
     rc = lib.mdil_boundary_count(pd.data_ptr(), td.data_ptr(), N, H, W, nc, (C.c_int * len(widths))(*widths),
-                                 len(widths), ign, base + off_w, need, base + off_p, base + off_t,
+                                 len(widths), ign, arena.ptr("workspace"), need, arena.ptr("dist_pred"),
+                                 arena.ptr("dist_target"),
                                  *(counters[k].data_ptr() for k in B.COUNTERS),
                                  torch.cuda.current_stream().cuda_stream)
     assert rc == 0, lib.mdil_boundary_last_error()
     torch.cuda.synchronize()
-    host = arena.cpu().numpy()
-    written = np.zeros(total, dtype=bool)
-    written[off_p:off_p + npx] = written[off_t:off_t + npx] = True
-    written[off_w:off_w + 2 * npx] = True                      # the capped run distances of both maps
-    assert (host[~written] == 0xA5).all()
-    assert np.array_equal(host[off_p:off_p + npx].reshape(p.shape), dp)
-    assert np.array_equal(host[off_t:off_t + npx].reshape(p.shape), dt)
+    arena.read()
+    arena.assert_untouched(("dist_pred", "dist_target", "workspace"))
+    assert (arena.cut("workspace")[2 * npx:] == 0xA5).all()    # used: the capped run distances of both maps
+    assert np.array_equal(arena.cut("dist_pred").numpy().reshape(p.shape), dp)
+    assert np.array_equal(arena.cut("dist_target").numpy().reshape(p.shape), dt)
     check_counters({k: v.cpu().numpy() for k, v in counters.items()}, want)
 
 
 @pytest.fixture(scope="module")
 def tiny_model(dev):
-    from mdil_ss_amd.models.erfnet_RA_parallel import Net as Net_RAP
-    torch.manual_seed(0)
-    return Net_RAP([20, 20], 2, 1).to(dev).eval()
+    return HC.tiny_model(dev)
 
 
 def test_every_bin_together_is_the_confusion_matrix_of_fullres(dev):
@@ -303,7 +291,7 @@ def test_cli_end_to_end(dev, tiny_model, tmp_path):
     from mdil_ss_amd.dataset import ProceduralSeg
     ckpt, maps, bands = tmp_path / "checkpoint.pth.tar", tmp_path / "maps", tmp_path / "bands"
     first, second = tmp_path / "first.json", tmp_path / "second.json"
-    torch.save({"state_dict": {"module." + k: v.cpu() for k, v in tiny_model.state_dict().items()}}, ckpt)
+    HC.save_checkpoint(tiny_model, ckpt)
     data = ["--num-classes", "20", "20", "--task", "1", "--synthetic", "3", "--native-height", "96",
             "--native-width", "200", "--height", "64", "--width", "128"]
     a = B.main(B.build_parser().parse_args(data + ["--state", str(ckpt), "--widths", "1", "3", "8", "--score", "--json",

@@ -2,11 +2,12 @@
 (mdil_ss_amd/calibrate.py), against the fp64 reference of tests/calib_reference.py:
 ``F.conv_transpose2d`` in double, ``log_softmax(l / T)``, then confidence, NLL, Brier score and entropy.
 
-Inputs.  ``case(nc, shape, ignore_last)`` of tests/calib_reference.py: the draw of
-tests/test_predict_gpu.py (seed 10 nc + H), targets sampled per pixel from softmax(l64 / 1.7) (seed
-7 nc + W), about 2 % of them set to the ignore index (nc - 1 or 255) and, with 255, about 1 % to an
-id out of range.  16 temperatures, geometric on [0.25, 4].  tests/test_calib_cpu.py checks on the
-CPU that the NLL of every case is unimodal in T and where its minimum lies.
+Inputs.  ``case(nc, shape, ignore_last)`` of tests/calib_reference.py: ``head_inputs`` of
+tests/head_cases.py, the case of the predict suite (seed 10 nc + H), targets sampled per pixel from
+softmax(l64 / 1.7) (seed 7 nc + W), about 2 % of them set to the ignore index (nc - 1 or 255) and,
+with 255, about 1 % to an id out of range.  16 temperatures, geometric on [0.25, 4].
+tests/test_calib_cpu.py checks on the CPU that the NLL of every case is unimodal in T and where its
+minimum lies.
 
 Tolerances, with S = max_c (|b| + sum |x| |w|) of the pixel and U = 2^-24:
     conf   K_CONF  U (1 + S / T)
@@ -28,13 +29,12 @@ import torch
 import torch.nn.functional as F
 
 from tests import calib_reference as R
+from tests import head_cases as HC
+from tests.head_cases import CLASSES, SHAPES, U, as_bytes, host, nhwc, predict_labels
 
 pytestmark = pytest.mark.gpu
 
-U = R.U
-GAMMA17 = 17 * U / (1 - 17 * U)
 MAX_EXCLUDED = 1e-3
-CLASSES, SHAPES = R.CLASSES, R.SHAPES
 TEMPS = tuple(0.25 * 16 ** (i / 15) for i in range(16))
 # Worst per-pixel constants of the dense fp32 torch route measured on an MI355X over the 32 cases
 # and 16 temperatures: conf 2.767 and nll 3.232 (nc 2, shape (3, 16, 48)), brier 2.920 (the same
@@ -52,13 +52,7 @@ IGNORES = (True, False)                              # the ignore index is nc - 
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "the calibration path needs an MI355X"
-    import mdil_ss_amd  # noqa: F401
-    return torch.device("cuda", 0)
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
+    return HC.device("calibration")
 
 
 @functools.lru_cache(maxsize=None)
@@ -67,9 +61,7 @@ def reference(nc, shape, ignore_last):
     modified): conf, nll, brier, ent [16,N,2H,2W] (nll and brier 0 where not counted), label, near."""
     c = R.case(nc, shape, ignore_last)
     per_t = [R.stats64(c["logits"], c["target"], c["counted"], T) for T in TEMPS]
-    top, idx = c["logits"].topk(2, dim=1)
-    Sc = F.conv_transpose2d(c["x"].double().abs(), c["w"].double().abs(), c["b"].double().abs(), stride=2)
-    near = (top[:, 0] - top[:, 1]) <= 2 * GAMMA17 * Sc.gather(1, idx).max(1)[0]
+    near = HC.near_tie(*HC.head64(c["x"], c["w"], c["b"]), 17)
     scale = torch.stack([U * (1 + c["S"] / T) for T in TEMPS])
     out = {k: torch.stack([s[i] for s in per_t]) for i, k in ((0, "conf"), (2, "nll"), (3, "brier"), (4, "ent"))}
     out.update(label=c["logits"].max(1)[1], near=near, tol_conf=scale, tol_nll=scale * (1 + out["nll"].abs()),
@@ -90,10 +82,6 @@ def new_counters(dev, nc, shape, K, bins=15, class_hist=True, fill=0):
     if class_hist:
         c["class_hist"] = z(nc, bins, 3)
     return c
-
-
-def host(d):
-    return {k: (None if v is None else v.cpu()) for k, v in d.items() if k != "workspace"}
 
 
 def run(dev, c, temps=TEMPS, bins=15, class_temp=None, counters=None, calls=1, **over):
@@ -120,26 +108,6 @@ def full(dev, nc, shape, ignore_last):
     return out, once, twice
 
 
-def as_bytes(t):
-    return t.contiguous().view(torch.uint8) if t.dtype != torch.uint8 else t
-
-
-def predict_labels(dev, x, w, b):
-    from mdil_ss_amd.predict import predict_head
-    label = predict_head(nhwc(x).to(dev), w.to(dev), b.to(dev), None, False)[0]
-    torch.cuda.synchronize()
-    return label.cpu()
-
-
-def check_labels(got, want, near, what):
-    share = near.double().mean().item()
-    print(f"{what}: excluded {int(near.sum())} of {near.numel()} pixels")
-    assert share <= MAX_EXCLUDED, f"{what}: {share:.2%} of the pixels are fp32 near-ties"
-    assert got.dtype == torch.uint8 and tuple(got.shape) == tuple(want.shape)
-    wrong = (got.long() != want) & ~near
-    assert not wrong.any(), f"{what}: {int(wrong.sum())} of {wrong.numel()} labels differ from the fp64 argmax"
-
-
 def expected_hist(c, conf, label, bins, rows=None):
     """The histogram the library's rule gives for the kernel's own fp32 confidences [N,h,w] and labels:
     [bins,3], or with ``rows`` = nc one per predicted class [nc,bins,3]."""
@@ -160,7 +128,7 @@ def test_labels_are_predict_heads_and_match_fp64(dev, nc, shape, ignore_last):
     ref = reference(nc, shape, ignore_last)
     out, _, _ = full(dev, nc, shape, ignore_last)
     assert torch.equal(out["label"], predict_labels(dev, c["x"], c["w"], c["b"]))
-    check_labels(out["label"], ref["label"], ref["near"], f"nc {nc} shape {shape}")
+    HC.check_labels(out["label"], ref["label"], ref["near"], f"nc {nc} shape {shape}", HC.share(MAX_EXCLUDED))
 
 
 # -------------------------------------------------------------------------------------- 2. maps
@@ -286,12 +254,7 @@ def test_two_calls_and_a_side_stream_give_the_same_bytes(dev):
     c = R.case(nc, shape, True)
     first_out, first_c, _ = full(dev, nc, shape, True)
     second_out, second_c = run(dev, c, class_temp=0, counters=new_counters(dev, nc, shape, 16))
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        side_c = new_counters(dev, nc, shape, 16)
-        side.synchronize()
-        third_out, third_c = run(dev, c, class_temp=0, counters=side_c)
-    side.synchronize()
+    third_out, third_c = HC.side_stream(lambda: run(dev, c, class_temp=0, counters=new_counters(dev, nc, shape, 16)))
     for out, cn in ((second_out, second_c), (third_out, third_c)):
         for k in first_out:
             assert torch.equal(as_bytes(out[k]), as_bytes(first_out[k])), k
@@ -314,18 +277,14 @@ def test_null_outputs_and_guard_bands_stay_untouched(dev, shape):
     npx = N * 4 * H * W
     base, added, _ = full(dev, nc, shape, True)
     sizes = {"label": npx, "conf": 4 * K * npx, "nll": 4 * K * npx}
-    off, pos = {}, 256
-    for k, n in sizes.items():
-        off[k] = pos
-        pos = (pos + n + 256 + 15) // 16 * 16
     x, w, b, tgt = on(dev, c)
     temps = (C.c_float * K)(*TEMPS)
     names = ("hist", "class_hist", "sums", "nonfinite", "bad_targets")
     for maps, passed in (((), ()), (("label",), ("bad_targets",)), (("conf",), ("hist", "nonfinite")),
                          (("nll",), ("class_hist", "sums")), (tuple(sizes), names)):
-        arena = torch.full((pos,), 0xA5, dtype=torch.uint8, device=dev)
+        arena = HC.Arena(dev, sizes)
         cn = new_counters(dev, nc, shape, K, fill=7)
-        p = lambda k: arena.data_ptr() + off[k] if k in maps else None  # noqa: E731
+        p = lambda k: arena.ptr(k) if k in maps else None               # noqa: E731
         q = lambda k: cn[k].data_ptr() if k in passed else None         # noqa: E731
         rc = lib.mdil_calib_head(x.data_ptr(), w.data_ptr(), b.data_ptr(), N, H, W, nc, tgt.data_ptr(), c["ignore"], temps,
                                  K, 15, 0 if "class_hist" in passed else -1, p("label"), p("conf"), p("nll"),
@@ -333,13 +292,11 @@ def test_null_outputs_and_guard_bands_stay_untouched(dev, shape):
                                  torch.cuda.current_stream().cuda_stream)
         assert rc == 0, lib.mdil_calib_last_error()
         torch.cuda.synchronize()
-        got, cn = arena.cpu(), host(cn)
-        written = torch.zeros(pos, dtype=torch.bool)
+        arena.read()
+        cn = host(cn)
+        arena.assert_untouched(maps, (maps, passed))
         for k in maps:
-            written[off[k]:off[k] + sizes[k]] = True
-        assert (got[~written] == 0xA5).all(), (maps, passed)
-        for k in maps:
-            assert torch.equal(got[off[k]:off[k] + sizes[k]], as_bytes(base[k]).reshape(-1)), k
+            assert torch.equal(arena.cut(k), as_bytes(base[k]).reshape(-1)), k
         for k in names:
             want = 7 + added[k] if k in passed else torch.full_like(cn[k], 7)
             assert torch.equal(cn[k], want.to(cn[k].dtype)), (k, maps, passed)
@@ -444,27 +401,7 @@ def test_fit_on_the_device(dev):
 # -------------------------------------------------------------------- 10. the shipped forward
 @pytest.fixture(scope="module")
 def models(dev):
-    """tests/test_drift_gpu.py's pair: (teacher [20], student [20, 20] initialised from it and then
-    perturbed), on the device, eval mode."""
-    from mdil_ss_amd.models.erfnet_RA_parallel import Net as Net_RAP
-    from oracle import fixtures as fx
-    from oracle import rap_oracle as O
-    torch.manual_seed(1)
-    teacher = Net_RAP([20], 1, 0)
-    t_sd = {k: v.clone() for k, v in teacher.state_dict().items()}
-    fx.perturb_bn(t_sd, 11)
-    teacher.load_state_dict(t_sd)
-    torch.manual_seed(0)
-    student = Net_RAP([20, 20], 2, 1)
-    s_sd = {k: v.clone() for k, v in student.state_dict().items()}
-    for k, v in O.student_init_from_teacher(t_sd, s_sd, 1).items():
-        s_sd[k].copy_(v)
-    student.load_state_dict(s_sd)
-    g = torch.Generator().manual_seed(7)
-    with torch.no_grad():
-        for p in student.parameters():
-            p.mul_(1 + 0.05 * torch.randn(p.shape, generator=g))
-    return teacher.to(dev).eval(), student.to(dev).eval()
+    return HC.teacher_student(dev)
 
 
 @pytest.mark.parametrize("which", (0, 1))
@@ -513,7 +450,7 @@ def test_cli_end_to_end(dev, models, tmp_path):
     from mdil_ss_amd import calibrate as K
     _, student = models
     ckpt = tmp_path / "model.pth.tar"
-    torch.save({"state_dict": {"module." + k: v.cpu() for k, v in student.state_dict().items()}}, ckpt)
+    HC.save_checkpoint(student, ckpt)
     base = ["--state", str(ckpt), "--num-classes", "20", "20", "--task", "0", "--synthetic", "2", "--height", "64",
             "--width", "128", "--fit"]
     first = K.main(K.build_parser().parse_args(base + ["--out", str(tmp_path / "o"), "--json", str(tmp_path / "a.json")]))

@@ -3,10 +3,11 @@
 both models, ``log_softmax``, then ``kl = sum_c p^A_c (z^A_c - z^B_c)`` and
 ``kd = sum_c p^A_c (z^A_c - p^B_c)``.
 
-Inputs.  A is ``case(nc, shape)`` of tests/test_predict_gpu.py re-stated (seed 10 nc + H); the same
-draw with seed 10 nc + H + 1000 gives (x', w', b'); B = (x + 0.1 x', w + 0.05 w', b).  No pixel of A
-or B is an fp32 near-tie (the 2 gamma_17 S rule of tests/test_predict_gpu.py) in the 16 cases, 8 of
-2.1 M are at (1, 513, 1023) with two classes, and A and B disagree on 3 to 13 % of the pixels.
+Inputs.  A is ``head_inputs(nc, shape)`` of tests/head_cases.py, the case of the predict suite (seed
+10 nc + H); the same draw with seed 10 nc + H + 1000 gives (x', w', b'); B = (x + 0.1 x', w + 0.05 w',
+b).  No pixel of A or B is an fp32 near-tie (the 2 gamma_17 S rule of tests/head_cases.py) in the 16
+cases, 8 of 2.1 M are at (1, 513, 1023) with two classes, and A and B disagree on 3 to 13 % of the
+pixels.
 
 Tolerance of kl and kd.  Per pixel ``K 2^-24 (1 + S^A + S^B) (1 + share)``, S^M the largest
 ``|b| + sum |x| |w|`` over the classes of the pixel, share = ``sum_c p^A_c |z^A_c - z^B_c|`` for kl
@@ -26,13 +27,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import head_cases as HC
+from tests.head_cases import CLASSES, SHAPES, U, as_bytes, host, make_target, nhwc, predict_labels
+
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
-GAMMA17 = 17 * U / (1 - 17 * U)
 MAX_EXCLUDED = 1e-3
-CLASSES = (2, 20, 27, 32)
-SHAPES = ((1, 1, 1), (1, 9, 7), (2, 12, 20), (3, 16, 48))
+LIMIT = HC.share(MAX_EXCLUDED)
 # Worst constants of the dense fp32 torch route measured on an MI355X over the 16 cases: kl 3.034
 # (nc 32, shape (2, 12, 20)), kd 1.703 (nc 27, shape (2, 12, 20)); per case 0.17 ... 3.03 and
 # 0.11 ... 1.70.  The kernel's own kl constant over the same cases was 0.34 ... 5.03 (worst at nc 27,
@@ -45,40 +46,21 @@ K_KL, K_KD = 4 * K_KL_TORCH, 4 * K_KD_TORCH
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "the drift path needs an MI355X"
-    import mdil_ss_amd  # noqa: F401
-    return torch.device("cuda", 0)
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
-def draw(nc, shape, seed):
-    """tests/test_predict_gpu.py::case's draw."""
-    N, H, W = shape
-    g = torch.Generator().manual_seed(seed)
-    w = torch.randn(16, nc, 2, 2, generator=g) * 0.3
-    b = torch.randn(nc, generator=g) * 0.2
-    x = F.relu(torch.randn(N, 16, H, W, generator=g))
-    return x, w, b
+    return HC.device("drift")
 
 
 @functools.lru_cache(maxsize=None)
 def pair(nc, shape):
     """-> ((xa, wa, ba), (xb, wb, bb)), x as [N,16,H,W]; never modified."""
-    xa, wa, ba = draw(nc, shape, 10 * nc + shape[1])
-    xp, wp, _ = draw(nc, shape, 10 * nc + shape[1] + 1000)
+    xa, wa, ba = HC.head_inputs(nc, shape)
+    xp, wp, _ = HC.draw(nc, shape, HC.case_seed(nc, shape) + 1000)
     return (xa, wa, ba), (xa + 0.1 * xp, wa + 0.05 * wp, ba.clone())
 
 
-def head64(x, w, b):
+def reference_head(x, w, b):
     """-> (fp64 logits [N,nc,2H,2W], S [N,2H,2W], fp64 argmax, near-tie mask)."""
-    logits = F.conv_transpose2d(x.double(), w.double(), b.double(), stride=2)
-    S = F.conv_transpose2d(x.double().abs(), w.double().abs(), b.double().abs(), stride=2)
-    top, idx = logits.topk(2, dim=1)
-    near = (top[:, 0] - top[:, 1]) <= 2 * GAMMA17 * S.gather(1, idx).max(1)[0]
-    return logits, S.max(1)[0], logits.max(1)[1], near
+    logits, S = HC.head64(x, w, b)
+    return logits, S.max(1)[0], logits.max(1)[1], HC.near_tie(logits, S, 17)
 
 
 def divergences(la, lb):
@@ -90,8 +72,8 @@ def divergences(la, lb):
 
 
 def reference_of(a, b):
-    la, Sa, label_a, near_a = head64(*a)
-    lb, Sb, label_b, near_b = head64(*b)
+    la, Sa, label_a, near_a = reference_head(*a)
+    lb, Sb, label_b, near_b = reference_head(*b)
     kl, kd, share_kl, share_kd = divergences(la, lb)
     scale = U * (1 + Sa + Sb)
     return dict(label_a=label_a, label_b=label_b, near_a=near_a, near_b=near_b, kl=kl, kd=kd,
@@ -119,10 +101,6 @@ def new_counters(dev, nc, shape, scored, fill=0):
     return c
 
 
-def host(d):
-    return {k: (None if v is None else v.cpu()) for k, v in d.items() if k != "workspace"}
-
-
 def run(dev, a, b, target=None, ignore=-1, counters=None, calls=1):
     """-> (maps, counters) on the host after ``calls`` calls into the same counters."""
     from mdil_ss_amd.drift import drift_head
@@ -141,22 +119,6 @@ def plain(dev, nc, shape):
     return run(dev, a, b, counters=new_counters(dev, nc, shape, False))
 
 
-def predict_labels(dev, x, w, b):
-    from mdil_ss_amd.predict import predict_head
-    label = predict_head(nhwc(x).to(dev), w.to(dev), b.to(dev), None, False)[0]
-    torch.cuda.synchronize()
-    return label.cpu()
-
-
-def check_labels(got, want, near, what):
-    share = near.double().mean().item()
-    print(f"{what}: excluded {int(near.sum())} of {near.numel()} pixels")
-    assert share <= MAX_EXCLUDED, f"{what}: {share:.2%} of the pixels are fp32 near-ties"
-    assert got.dtype == torch.uint8 and tuple(got.shape) == tuple(want.shape)
-    wrong = (got.long() != want) & ~near
-    assert not wrong.any(), f"{what}: {int(wrong.sum())} of {wrong.numel()} labels differ from the fp64 argmax"
-
-
 # ------------------------------------------------------------------------------------ 1. labels
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("nc", CLASSES)
@@ -166,8 +128,8 @@ def test_labels_are_predict_heads_and_match_fp64(dev, nc, shape):
     out, _ = plain(dev, nc, shape)
     assert torch.equal(out["label_a"], predict_labels(dev, *a))
     assert torch.equal(out["label_b"], predict_labels(dev, *b))
-    check_labels(out["label_a"], ref["label_a"], ref["near_a"], f"nc {nc} shape {shape} A")
-    check_labels(out["label_b"], ref["label_b"], ref["near_b"], f"nc {nc} shape {shape} B")
+    HC.check_labels(out["label_a"], ref["label_a"], ref["near_a"], f"nc {nc} shape {shape} A", LIMIT)
+    HC.check_labels(out["label_b"], ref["label_b"], ref["near_b"], f"nc {nc} shape {shape} B", LIMIT)
     differ = (out["label_a"] != out["label_b"]).double().mean().item()
     print(f"nc {nc} shape {shape}: A and B disagree on {differ:.2%} of the pixels")
 
@@ -247,18 +209,6 @@ def test_kl_map_matches_fp64(dev, nc, shape):
 
 
 # ------------------------------------------------------------------------------------ 5. counts
-def make_target(nc, shape, ignore, seed):
-    """tests/test_fullres_gpu.py::make_target: u8 targets in [0, nc) with some ignore pixels and a
-    few values >= nc."""
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randint(0, nc, shape, generator=g, dtype=torch.uint8)
-    r = torch.rand(shape, generator=g)
-    t[r < 0.10] = ignore
-    t[(r >= 0.10) & (r < 0.12)] = nc                    # out of range
-    t[(r >= 0.12) & (r < 0.13)] = 200
-    return t
-
-
 def expected(nc, label_a, label_b, target, ignore):
     """The counters and the change map from the kernel's own labels and the target, by bincount."""
     la, lb = label_a.reshape(-1).long(), label_b.reshape(-1).long()
@@ -358,22 +308,14 @@ def test_sums(dev, nc, shape, ignore):
 
 
 # ------------------------------------------------------------------------------- 7. determinism
-def as_bytes(t):
-    return t.contiguous().view(torch.uint8) if t.dtype != torch.uint8 else t
-
-
 @pytest.mark.parametrize("ignore", (None, "last"))
 def test_two_calls_and_a_side_stream_give_the_same_bytes(dev, ignore):
     nc, shape = 27, (3, 16, 48)
     a, b = pair(nc, shape)
     target, ign, first_out, first_c, _ = scored(dev, nc, shape, ignore)
     second_out, second_c = run(dev, a, b, target, ign, new_counters(dev, nc, shape, target is not None))
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        side_c = new_counters(dev, nc, shape, target is not None)
-        side.synchronize()
-        third_out, third_c = run(dev, a, b, target, ign, side_c)
-    side.synchronize()
+    third_out, third_c = HC.side_stream(
+        lambda: run(dev, a, b, target, ign, new_counters(dev, nc, shape, target is not None)))
     for out, c in ((second_out, second_c), (third_out, third_c)):
         for k in first_out:
             assert torch.equal(as_bytes(out[k]), as_bytes(first_out[k])), k
@@ -395,19 +337,15 @@ def test_null_outputs_and_guard_bands_stay_untouched(dev, shape):
     target, _, _, scored_c, _ = scored(dev, nc, shape, "last")
     base, plain_c = plain(dev, nc, shape)
     sizes = {"label_a": npx, "label_b": npx, "kl": 4 * npx, "change": npx}
-    off, pos = {}, 256
-    for k, n in sizes.items():
-        off[k] = pos
-        pos = (pos + n + 256 + 15) // 16 * 16
     args = on(dev, a, b)
     tgt = target.to(dev)
     names = ("transition", "confusion_a", "confusion_b", "outcome", "bad_targets", "sums")
     for maps, with_target, passed in (((), False, ()), (("label_b",), False, ("bad_targets",)),
                                       (("kl", "change"), False, ("transition", "sums", "bad_targets")),
                                       (tuple(sizes), True, names)):
-        arena = torch.full((pos,), 0xA5, dtype=torch.uint8, device=dev)
+        arena = HC.Arena(dev, sizes)
         c = new_counters(dev, nc, shape, True, fill=7)
-        p = lambda k: arena.data_ptr() + off[k] if k in maps else None  # noqa: E731
+        p = lambda k: arena.ptr(k) if k in maps else None               # noqa: E731
         q = lambda k: c[k].data_ptr() if k in passed else None          # noqa: E731
         rc = lib.mdil_drift_head(*(t.data_ptr() for t in args), N, H, W, nc, tgt.data_ptr() if with_target else None,
                                  nc - 1, p("label_a"), p("label_b"), p("kl"), p("change"), *(q(k) for k in names),
@@ -415,12 +353,10 @@ def test_null_outputs_and_guard_bands_stay_untouched(dev, shape):
                                  torch.cuda.current_stream().cuda_stream)
         assert rc == 0, lib.mdil_drift_last_error()
         torch.cuda.synchronize()
-        got, c = arena.cpu(), host(c)
-        written = torch.zeros(pos, dtype=torch.bool)
-        for k in maps:
-            written[off[k]:off[k] + sizes[k]] = True
-        assert (got[~written] == 0xA5).all(), (maps, with_target)
-        cut = lambda k: got[off[k]:off[k] + sizes[k]]                   # noqa: E731
+        arena.read()
+        c = host(c)
+        arena.assert_untouched(maps, (maps, with_target))
+        cut = arena.cut
         for k in ("label_a", "label_b"):
             if k in maps:
                 assert torch.equal(cut(k), base[k].reshape(-1))
@@ -449,8 +385,8 @@ def test_grid_stride_loop_past_the_grid_bound(dev):
     out, c = run(dev, a, b, target, 255, new_counters(dev, nc, shape, True))
     assert torch.equal(out["label_a"], predict_labels(dev, *a)) and torch.equal(out["label_b"], predict_labels(dev, *b))
     for m, which in ((a, "a"), (b, "b")):
-        _, _, label, near = head64(*m)
-        check_labels(out["label_" + which], label, near, f"nc {nc} shape {shape} {which.upper()}")
+        _, _, label, near = reference_head(*m)
+        HC.check_labels(out["label_" + which], label, near, f"nc {nc} shape {shape} {which.upper()}", LIMIT)
     want = expected(nc, out["label_a"], out["label_b"], target, 255)
     assert want["bad_targets"] > 0
     check_counts(nc, out, c, want)
@@ -460,26 +396,7 @@ def test_grid_stride_loop_past_the_grid_bound(dev):
 # --------------------------------------------------------------------- 9. the shipped forward
 @pytest.fixture(scope="module")
 def models(dev):
-    """(teacher [20], student [20, 20] initialised from it and then perturbed), on the device, eval mode."""
-    from mdil_ss_amd.models.erfnet_RA_parallel import Net as Net_RAP
-    from oracle import fixtures as fx
-    from oracle import rap_oracle as O
-    torch.manual_seed(1)
-    teacher = Net_RAP([20], 1, 0)
-    t_sd = {k: v.clone() for k, v in teacher.state_dict().items()}
-    fx.perturb_bn(t_sd, 11)
-    teacher.load_state_dict(t_sd)
-    torch.manual_seed(0)
-    student = Net_RAP([20, 20], 2, 1)
-    s_sd = {k: v.clone() for k, v in student.state_dict().items()}
-    for k, v in O.student_init_from_teacher(t_sd, s_sd, 1).items():
-        s_sd[k].copy_(v)
-    student.load_state_dict(s_sd)
-    g = torch.Generator().manual_seed(7)
-    with torch.no_grad():
-        for p in student.parameters():
-            p.mul_(1 + 0.05 * torch.randn(p.shape, generator=g))
-    return teacher.to(dev).eval(), student.to(dev).eval()
+    return HC.teacher_student(dev)
 
 
 def test_agrees_with_the_shipped_forward(dev, models):
@@ -503,11 +420,10 @@ def test_agrees_with_the_shipped_forward(dev, models):
     assert report["pixels"] == report["counted_pixels"] == 2 * 64 * 128
     assert abs(report["kd_loss"] - want) <= 1e-3 * abs(want) + 1e-6
     for model, feat, logits, key in ((teacher, ft, lt, "label_a"), (student, fs, ls, "label_b")):
-        w, b = (t.detach().cpu().double() for t in model.head_params(0))
-        S = F.conv_transpose2d(feat.cpu().double().permute(0, 3, 1, 2).abs(), w.abs(), b.abs(), stride=2)
-        top, idx = logits.cpu().double().topk(2, dim=1)
-        near = (top[:, 0] - top[:, 1]) <= 2 * GAMMA17 * S.gather(1, idx).max(1)[0]
-        check_labels(out[key].cpu(), logits.max(1)[1].cpu(), near, f"shipped path {key}")
+        w, b = (t.detach().cpu() for t in model.head_params(0))
+        _, S = HC.head64(feat.cpu().permute(0, 3, 1, 2), w, b)
+        near = HC.near_tie(logits.cpu().double(), S, 17)
+        HC.check_labels(out[key].cpu(), logits.max(1)[1].cpu(), near, f"shipped path {key}", LIMIT)
     assert 0 < report["agreement"] < 1
 
 
@@ -522,7 +438,7 @@ def test_cli_end_to_end(dev, models, tmp_path):
     teacher, student = models
     out, report_file = tmp_path / "maps", tmp_path / "report.json"
     for model, name in ((teacher, "before.pth.tar"), (student, "after.pth.tar")):
-        torch.save({"state_dict": {"module." + k: v.cpu() for k, v in model.state_dict().items()}}, tmp_path / name)
+        HC.save_checkpoint(model, tmp_path / name)
     report = D.main(D.build_parser().parse_args(
         ["--before", str(tmp_path / "before.pth.tar"), "--before-num-classes", "20", "--after",
          str(tmp_path / "after.pth.tar"), "--after-num-classes", "20", "20", "--task", "0", "--synthetic", "3",

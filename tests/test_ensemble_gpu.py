@@ -14,23 +14,17 @@ import torch
 import torch.nn.functional as F
 
 from tests import ensemble_reference as R
-from tests.test_fullres_gpu import expected_counts, make_target, random_luts
+from tests import head_cases as HC
+from tests.head_cases import U, expected_counts, make_target, nhwc, random_luts
 
 pytestmark = pytest.mark.gpu
 
-U = R.U
 NCASES = range(len(R.CASES))
 
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "the ensemble path needs an MI355X"
-    import mdil_ss_amd  # noqa: F401
-    return torch.device("cuda", 0)
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
+    return HC.device("ensemble")
 
 
 def run(dev, xs, flips, w, b, size, mode, **kw):
@@ -49,26 +43,14 @@ def test_labels_match_fp64_argmax(dev, nc, index, mode):
     xs, w, b, flips, size, _, ref, excluded, _ = R.case(nc, index, mode)
     label, colour, conf = run(dev, xs, flips, w, b, size, mode)
     assert colour is None and conf is None
-    R.check_labels(label, ref, excluded, f"nc {nc} case {index} {mode}")
+    HC.check_labels(label, ref, excluded, f"nc {nc} case {index} {mode}", HC.count_cap)
 
 
 def check_confusion(dev, xs, flips, w, b, nc, size, mode, ignore):
     from mdil_ss_amd.ensemble import ensemble_head
-    N = xs[0].shape[0]
-    target = make_target(nc, (N,) + tuple(size), ignore, seed=nc + size[0])
-    conf = torch.zeros(nc, nc, dtype=torch.int64, device=dev)
-    bad = torch.zeros(1, dtype=torch.int64, device=dev)
     args = ([(nhwc(x).to(dev), bool(f)) for x, f in zip(xs, flips)], w.to(dev), b.to(dev), size)
-    kw = dict(mode=mode, target=target.to(dev), ignore_index=ignore, confusion=conf, bad_targets=bad)
-    label = ensemble_head(*args, **kw)[0].cpu()
-    matrix, n_bad, n_counted = expected_counts(target, label, nc, ignore)
-    assert n_bad > 0 or target.numel() < 50
-    assert torch.equal(conf.cpu(), matrix) and int(bad.item()) == n_bad
-    assert int(conf.sum().item()) == n_counted
-    again = ensemble_head(*args, **kw)[0].cpu()          # accumulates, does not overwrite
-    assert torch.equal(again, label)
-    assert torch.equal(conf.cpu(), 2 * matrix) and int(bad.item()) == 2 * n_bad
-    return label
+    head = lambda **kw: ensemble_head(*args, mode=mode, **kw)  # noqa: E731
+    return HC.check_confusion(head, dev, nc, xs[0].shape[0], size, ignore)
 
 
 @pytest.mark.parametrize("mode", R.MODES)
@@ -79,7 +61,7 @@ def test_grid_stride_loop_past_the_grid_bound(dev, mode):
     xs, w, b, flips, size, _, ref, excluded, _ = R.case(R.BIG_NC, -1, mode)
     assert size[0] * ((size[1] + 1) // 2) > 2 * 8192 * 64
     label = check_confusion(dev, xs, flips, w, b, R.BIG_NC, size, mode, 255)
-    R.check_labels(label, ref, excluded, f"bounded-grid case {mode}")
+    HC.check_labels(label, ref, excluded, f"bounded-grid case {mode}", HC.count_cap)
 
 
 @pytest.mark.parametrize("index", (0, 2, 4, 6))
@@ -130,7 +112,7 @@ def test_view_order_changes_labels_only_inside_the_exclusion(dev, index, mode):
     perm = perm if perm != list(range(len(xs))) else perm[::-1]
     second = run(dev, [xs[i] for i in perm], [flips[i] for i in perm], w, b, size, mode)[0]
     assert not ((first != second) & ~excluded).any()
-    R.check_labels(second, ref, excluded, f"nc {nc} case {index} {mode} permuted {perm}")
+    HC.check_labels(second, ref, excluded, f"nc {nc} case {index} {mode} permuted {perm}", HC.count_cap)
 
 
 @pytest.mark.parametrize("mode", R.MODES)
@@ -256,41 +238,31 @@ def test_null_outputs_and_guard_bands_stay_untouched(dev, index, mode):
     plain = plain.reshape(-1)
     N = xs[0].shape[0]
     npx = N * size[0] * size[1]
-    G = 256
-    off_l = G
-    off_c = (off_l + npx + G + 15) // 16 * 16
-    off_f = (off_c + 3 * npx + G + 15) // 16 * 16
-    total = (off_f + 4 * npx + G + 15) // 16 * 16
     feats = [nhwc(x).to(dev) for x in xs]
     table = _ensemble_lib.view_table([(f.data_ptr(), f.shape[1], f.shape[2], m) for f, m in zip(feats, flips)])
     wd, bd, idd, pd = w.to(dev), b.to(dev), ids.to(dev), pal.to(dev)
     target = make_target(nc, (N,) + size, nc - 1, seed=1).to(dev)
     for with_colour, with_conf, with_target in ((False, False, False), (True, False, False), (False, True, False),
                                                 (True, True, True)):
-        arena = torch.full((total,), 0xA5, dtype=torch.uint8, device=dev)
+        arena = HC.Arena(dev, {"label": npx, "colour": 3 * npx, "confidence": 4 * npx})
         conf = torch.full((nc, nc), 7, dtype=torch.int64, device=dev)
         bad = torch.full((1,), 5, dtype=torch.int64, device=dev)
-        base = arena.data_ptr()
         rc = lib.mdil_ensemble_head(table, len(feats), wd.data_ptr(), bd.data_ptr(), N, nc, size[0], size[1],
                                     _ensemble_lib.MODES[mode], idd.data_ptr(), pd.data_ptr(),
-                                    target.data_ptr() if with_target else None, nc - 1, base + off_l,
-                                    base + off_c if with_colour else None, base + off_f if with_conf else None,
+                                    target.data_ptr() if with_target else None, nc - 1, arena.ptr("label"),
+                                    arena.ptr("colour") if with_colour else None,
+                                    arena.ptr("confidence") if with_conf else None,
                                     conf.data_ptr(), bad.data_ptr(), torch.cuda.current_stream().cuda_stream)
         assert rc == 0, lib.mdil_ensemble_last_error()
         torch.cuda.synchronize()
-        host = arena.cpu()
-        written = torch.zeros(total, dtype=torch.bool)
-        written[off_l:off_l + npx] = True
+        arena.read()
+        on = (("label", True), ("colour", with_colour), ("confidence", with_conf))
+        arena.assert_untouched([k for k, given in on if given], (with_colour, with_conf, with_target))
+        assert torch.equal(arena.cut("label"), ids[plain.long()])
         if with_colour:
-            written[off_c:off_c + 3 * npx] = True
+            assert torch.equal(arena.cut("colour").reshape(-1, 3), pal[plain.long()])
         if with_conf:
-            written[off_f:off_f + 4 * npx] = True
-        assert (host[~written] == 0xA5).all(), (with_colour, with_conf, with_target)
-        assert torch.equal(host[off_l:off_l + npx], ids[plain.long()])
-        if with_colour:
-            assert torch.equal(host[off_c:off_c + 3 * npx].reshape(-1, 3), pal[plain.long()])
-        if with_conf:
-            assert torch.equal(host[off_f:off_f + 4 * npx].clone().view(torch.float32), conf_ref.reshape(-1))
+            assert torch.equal(arena.cut("confidence").clone().view(torch.float32), conf_ref.reshape(-1))
         if with_target:
             matrix, n_bad, _ = expected_counts(target.cpu(), plain, nc, nc - 1)
             assert torch.equal(conf.cpu(), matrix + 7) and int(bad.item()) == n_bad + 5
@@ -309,19 +281,14 @@ def test_side_stream_gives_the_same_bytes(dev, mode):
     kw = dict(mode=mode, id_map=ids.to(dev), palette=pal.to(dev), confidence=True)
     first = ensemble_head(*args, **kw)
     torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        second = ensemble_head(*args, **kw)
-    side.synchronize()
+    second = HC.side_stream(lambda: ensemble_head(*args, **kw))
     for a, c in zip(first, second):
         assert torch.equal(a.cpu(), c.cpu())
 
 
 @pytest.fixture(scope="module")
 def tiny_model(dev):
-    from mdil_ss_amd.models.erfnet_RA_parallel import Net as Net_RAP
-    torch.manual_seed(0)
-    return Net_RAP([20, 20], 2, 1).to(dev).eval()
+    return HC.tiny_model(dev)
 
 
 SCALES = (0.75, 1.0, 1.25)
@@ -374,7 +341,7 @@ def test_cli_end_to_end(dev, tiny_model, tmp_path):
     from mdil_ss_amd.dataset import ProceduralSeg
     from mdil_ss_amd.predict import default_palette
     ckpt, out, report_file = tmp_path / "checkpoint.pth.tar", tmp_path / "maps", tmp_path / "report.json"
-    torch.save({"state_dict": {"module." + k: v.cpu() for k, v in tiny_model.state_dict().items()}}, ckpt)
+    HC.save_checkpoint(tiny_model, ckpt)
     report = E.main(E.build_parser().parse_args(
         ["--state", str(ckpt), "--num-classes", "20", "20", "--task", "1", "--synthetic", "3", "--native-height", "96",
          "--native-width", "200", "--height", "64", "--width", "128", "--scales", "0.75", "1", "1.25", "--flip",

@@ -8,11 +8,10 @@ fp64 reference on the CPU:
 
 Which pixels may differ.  The kernel's header counts k = 68 roundings on the longest path from the
 inputs to a compared logit (two weight quotients, their product, the scaling of the feature, a
-64-term FMA chain), so its value is within gamma_k * Su of the exact one, gamma_k = k u / (1 - k u),
-u = 2^-24, and the order of two classes can flip only where their exact margin is at most
-2 * gamma_k * Su (Su of the larger of the two).  A pixel whose fp64 top-2 margin is within that bound
-is excluded, every other pixel must match the fp64 argmax exactly, and at most
-max(1, floor(0.001 * pixels)) pixels of a case may be excluded -- none in a case of fewer than 100."""
+64-term FMA chain), so the near-tie rule of tests/head_cases.py applies to Lu and Su with k = 68.  A
+pixel whose fp64 top-2 margin is within that bound is excluded, every other pixel must match the fp64
+argmax exactly, and at most max(1, floor(0.001 * pixels)) pixels of a case may be excluded -- none in
+a case of fewer than 100."""
 import functools
 import glob
 import json
@@ -24,13 +23,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import head_cases as HC
+from tests.head_cases import CLASSES, expected_counts, make_target, nhwc, random_luts
+
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U = 2.0 ** -24
 K = 68                                     # the kernel header's count; checked against its text below
-GAMMA = K * U / (1 - K * U)
-CLASSES = (2, 20, 27, 32)
 SIZES = {
     (1, 1, 1): ((1, 1), (2, 2), (5, 7)),
     (1, 9, 7): ((18, 14), (36, 28), (25, 31), (11, 9)),             # identity, 2x, odd, down
@@ -43,55 +42,22 @@ SOME = [((1, 1, 1), (5, 7)), ((1, 9, 7), (25, 31)), ((2, 12, 20), (48, 80)), ((3
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "the full-resolution path needs an MI355X"
-    import mdil_ss_amd  # noqa: F401
-    return torch.device("cuda", 0)
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
-@functools.lru_cache(maxsize=None)
-def inputs(nc, shape):
-    """Seeded inputs, drawn exactly as tests/test_predict_gpu.py::case draws them."""
-    N, H, W = shape
-    g = torch.Generator().manual_seed(10 * nc + H)
-    w = torch.randn(16, nc, 2, 2, generator=g) * 0.3
-    b = torch.randn(nc, generator=g) * 0.2
-    x = F.relu(torch.randn(N, 16, H, W, generator=g))
-    return x, w, b
+    return HC.device("full-resolution")
 
 
 def reference(x, w, b, size):
     """-> (label i64 [N,Ho,Wo], excluded bool) from fp64 logits resized in fp64."""
-    L = F.conv_transpose2d(x.double(), w.double(), b.double(), stride=2)
-    S = F.conv_transpose2d(x.double().abs(), w.double().abs(), b.double().abs(), stride=2)
+    L, S = HC.head64(x, w, b)
     Lu = F.interpolate(L, size, mode="bilinear", align_corners=False)
     Su = F.interpolate(S, size, mode="bilinear", align_corners=False)
-    top, idx = Lu.topk(2, dim=1)
-    bound = 2 * GAMMA * Su.gather(1, idx).max(1)[0]
-    return Lu.max(1)[1], (top[:, 0] - top[:, 1]) <= bound
+    return Lu.max(1)[1], HC.near_tie(Lu, Su, K)
 
 
 @functools.lru_cache(maxsize=None)
 def case(nc, shape, size):
     """Inputs and their reference, computed once and shared (never modified)."""
-    x, w, b = inputs(nc, shape)
+    x, w, b = HC.head_inputs(nc, shape)
     return (x, w, b) + reference(x, w, b, size)
-
-
-def cap(pixels):
-    return 0 if pixels < 100 else max(1, pixels // 1000)
-
-
-def check_labels(label, ref, excluded, what):
-    n_ex = int(excluded.sum())
-    print(f"{what}: excluded {n_ex} of {excluded.numel()} pixels (cap {cap(excluded.numel())})")
-    assert n_ex <= cap(excluded.numel()), f"{what}: {n_ex} pixels are fp32 near-ties"
-    assert label.dtype == torch.uint8 and tuple(label.shape) == tuple(ref.shape)
-    wrong = (label.long() != ref) & ~excluded
-    assert not wrong.any(), f"{what}: {int(wrong.sum())} of {wrong.numel()} labels differ from the fp64 argmax"
 
 
 def run(dev, x, w, b, size, **kw):
@@ -100,16 +66,6 @@ def run(dev, x, w, b, size, **kw):
     out = fullres_head(nhwc(x).to(dev), w.to(dev), b.to(dev), size, **kw)
     torch.cuda.synchronize()
     return tuple(None if t is None else t.cpu() for t in out)
-
-
-def random_luts(nc):
-    """(id_map u8 [nc], palette u8 [nc,3]) with a 255 and a duplicated row each."""
-    g = torch.Generator().manual_seed(nc)
-    ids = torch.randint(0, 256, (nc,), generator=g, dtype=torch.uint8)
-    pal = torch.randint(0, 256, (nc, 3), generator=g, dtype=torch.uint8)
-    ids[0], ids[nc - 1] = 255, ids[1]
-    pal[0], pal[nc - 1] = torch.tensor([255, 0, 255], dtype=torch.uint8), pal[1]
-    return ids, pal
 
 
 def test_header_states_the_rounding_count():
@@ -123,13 +79,13 @@ def test_labels_match_fp64_argmax(dev, nc, shape, size):
     x, w, b, ref, excluded = case(nc, shape, size)
     label, colour = run(dev, x, w, b, size)
     assert colour is None
-    check_labels(label, ref, excluded, f"nc {nc} shape {shape} -> {size}")
+    HC.check_labels(label, ref, excluded, f"nc {nc} shape {shape} -> {size}", HC.count_cap)
 
 
 def test_ties_go_to_the_lowest_class(dev):
     """Classes 3 and 11 with bit-identical weights and bias tie exactly at every pixel of a resized
     map too; with the largest bias they are also the winners almost everywhere."""
-    x, w, b = inputs(20, (2, 12, 20))
+    x, w, b = HC.head_inputs(20, (2, 12, 20))
     w, b = w.clone(), b.clone()
     b[3] = b.max() + 1.0
     w[:, 11], b[11] = w[:, 3], b[3]
@@ -144,7 +100,7 @@ def test_ties_go_to_the_lowest_class(dev):
 def test_nan_logits_give_the_first_nan_class(dev):
     """(45, 77) from 24 x 40 logits has no source coordinate that is a whole number, so every
     neighbour has a weight above zero and the footprint of a NaN is the fp64 reference's."""
-    x, w, b = inputs(20, (2, 12, 20))
+    x, w, b = HC.head_inputs(20, (2, 12, 20))
     size = (45, 77)
     clean = run(dev, x, w, b, size)[0]
     xn = x.clone()
@@ -165,7 +121,7 @@ def test_nan_logits_give_the_first_nan_class(dev):
 @pytest.mark.parametrize("shape, size", SOME)
 @pytest.mark.parametrize("nc", CLASSES)
 def test_id_map_and_palette_are_applied_after_the_argmax(dev, nc, shape, size):
-    x, w, b = inputs(nc, shape)
+    x, w, b = HC.head_inputs(nc, shape)
     ids, pal = random_luts(nc)
     plain = run(dev, x, w, b, size)[0]
     label, colour = run(dev, x, w, b, size, id_map=ids, palette=pal)
@@ -176,48 +132,17 @@ def test_id_map_and_palette_are_applied_after_the_argmax(dev, nc, shape, size):
     assert torch.equal(only_colour[0], plain) and torch.equal(only_colour[1], colour)
 
 
-def make_target(nc, shape, ignore, seed):
-    """u8 targets in [0, nc) with some ignore pixels and a few values >= nc."""
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randint(0, nc, shape, generator=g, dtype=torch.uint8)
-    r = torch.rand(shape, generator=g)
-    t[r < 0.10] = ignore
-    t[(r >= 0.10) & (r < 0.12)] = nc                    # out of range
-    t[(r >= 0.12) & (r < 0.13)] = 200
-    return t
-
-
-def expected_counts(target, label, nc, ignore):
-    t, p = target.reshape(-1).long(), label.reshape(-1).long()
-    counted = (t < nc) & (t != ignore)
-    matrix = torch.bincount(t[counted] * nc + p[counted], minlength=nc * nc).reshape(nc, nc)
-    return matrix, int(((t >= nc) & (t != ignore)).sum()), int(counted.sum())
-
-
 def check_confusion(dev, x, w, b, nc, size, ignore):
     from mdil_ss_amd.fullres import fullres_head
-    N = x.shape[0]
-    target = make_target(nc, (N,) + tuple(size), ignore, seed=nc + size[0])
-    conf = torch.zeros(nc, nc, dtype=torch.int64, device=dev)
-    bad = torch.zeros(1, dtype=torch.int64, device=dev)
     args = (nhwc(x).to(dev), w.to(dev), b.to(dev), size)
-    kw = dict(target=target.to(dev), ignore_index=ignore, confusion=conf, bad_targets=bad)
-    label = fullres_head(*args, **kw)[0].cpu()
-    matrix, n_bad, n_counted = expected_counts(target, label, nc, ignore)
-    assert n_bad > 0 or target.numel() < 50
-    assert torch.equal(conf.cpu(), matrix) and int(bad.item()) == n_bad
-    assert int(conf.sum().item()) == n_counted
-    again = fullres_head(*args, **kw)[0].cpu()           # accumulates, does not overwrite
-    assert torch.equal(again, label)
-    assert torch.equal(conf.cpu(), 2 * matrix) and int(bad.item()) == 2 * n_bad
-    return label
+    return HC.check_confusion(lambda **kw: fullres_head(*args, **kw), dev, nc, x.shape[0], size, ignore)
 
 
 @pytest.mark.parametrize("ignore", ("last", 255))
 @pytest.mark.parametrize("shape, size", SOME + [((1, 9, 7), (36, 28))])
 @pytest.mark.parametrize("nc", CLASSES)
 def test_confusion_counts_the_kernels_own_labels(dev, nc, shape, size, ignore):
-    x, w, b = inputs(nc, shape)
+    x, w, b = HC.head_inputs(nc, shape)
     label = check_confusion(dev, x, w, b, nc, size, nc - 1 if ignore == "last" else 255)
     assert torch.equal(label, run(dev, x, w, b, size)[0])
 
@@ -225,7 +150,7 @@ def test_confusion_counts_the_kernels_own_labels(dev, nc, shape, size, ignore):
 def test_confusion_meter(dev):
     from mdil_ss_amd.fullres import ConfusionMeter
     nc, shape, size = 20, (2, 12, 20), (45, 77)
-    x, w, b = inputs(nc, shape)
+    x, w, b = HC.head_inputs(nc, shape)
     args = (nhwc(x).to(dev), w.to(dev), b.to(dev))
     target = make_target(nc, (2,) + size, nc - 1, seed=5)
     clean = target.clone()
@@ -252,37 +177,28 @@ def test_null_outputs_and_guard_bands_stay_untouched(dev, size):
     from mdil_ss_amd import _fullres_lib
     lib = _fullres_lib.load()
     nc, shape = 27, (1, 9, 7) if size == (25, 31) else (2, 12, 20)
-    x, w, b = inputs(nc, shape)
+    x, w, b = HC.head_inputs(nc, shape)
     ids, pal = random_luts(nc)
     plain = run(dev, x, w, b, size)[0].reshape(-1)
     N, _, H, W = x.shape
     npx = N * size[0] * size[1]
-    G = 256
-    off_l = G
-    off_c = (off_l + npx + G + 15) // 16 * 16
-    total = (off_c + 3 * npx + G + 15) // 16 * 16
     xd, wd, bd, idd, pd = nhwc(x).to(dev), w.to(dev), b.to(dev), ids.to(dev), pal.to(dev)
     target = make_target(nc, (N,) + size, nc - 1, seed=1).to(dev)
     for with_colour, with_target in ((False, False), (True, False), (True, True)):
-        arena = torch.full((total,), 0xA5, dtype=torch.uint8, device=dev)
+        arena = HC.Arena(dev, {"label": npx, "colour": 3 * npx})
         conf = torch.full((nc, nc), 7, dtype=torch.int64, device=dev)
         bad = torch.full((1,), 5, dtype=torch.int64, device=dev)
-        base = arena.data_ptr()
         rc = lib.mdil_fullres_head(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), N, H, W, nc, size[0], size[1],
                                    idd.data_ptr(), pd.data_ptr(), target.data_ptr() if with_target else None, nc - 1,
-                                   base + off_l, base + off_c if with_colour else None, conf.data_ptr(),
+                                   arena.ptr("label"), arena.ptr("colour") if with_colour else None, conf.data_ptr(),
                                    bad.data_ptr(), torch.cuda.current_stream().cuda_stream)
         assert rc == 0, lib.mdil_fullres_last_error()
         torch.cuda.synchronize()
-        host = arena.cpu()
-        written = torch.zeros(total, dtype=torch.bool)
-        written[off_l:off_l + npx] = True
+        arena.read()
+        arena.assert_untouched(("label", "colour") if with_colour else ("label",), (with_colour, with_target))
+        assert torch.equal(arena.cut("label"), ids[plain.long()])
         if with_colour:
-            written[off_c:off_c + 3 * npx] = True
-        assert (host[~written] == 0xA5).all(), (with_colour, with_target)
-        assert torch.equal(host[off_l:off_l + npx], ids[plain.long()])
-        if with_colour:
-            assert torch.equal(host[off_c:off_c + 3 * npx].reshape(-1, 3), pal[plain.long()])
+            assert torch.equal(arena.cut("colour").reshape(-1, 3), pal[plain.long()])
         if with_target:
             matrix, n_bad, _ = expected_counts(target.cpu(), plain, nc, nc - 1)
             assert torch.equal(conf.cpu(), matrix + 7) and int(bad.item()) == n_bad + 5
@@ -298,31 +214,26 @@ def test_grid_stride_loop_past_the_grid_bound(dev):
     assert size[0] * ((size[1] + 3) // 4) > 2048 * 256
     x, w, b, ref, excluded = case(nc, shape, size)
     label = check_confusion(dev, x, w, b, nc, size, 255)
-    check_labels(label, ref, excluded, f"nc {nc} shape {shape} -> {size}")
+    HC.check_labels(label, ref, excluded, f"nc {nc} shape {shape} -> {size}", HC.count_cap)
 
 
 def test_side_stream_gives_the_same_bytes(dev):
     from mdil_ss_amd.fullres import fullres_head
     nc, size = 27, (90, 135)
-    x, w, b = inputs(nc, (3, 16, 48))
+    x, w, b = HC.head_inputs(nc, (3, 16, 48))
     ids, pal = random_luts(nc)
     args = (nhwc(x).to(dev), w.to(dev), b.to(dev), size)
     kw = dict(id_map=ids.to(dev), palette=pal.to(dev))
     first = fullres_head(*args, **kw)
     torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        second = fullres_head(*args, **kw)
-    side.synchronize()
+    second = HC.side_stream(lambda: fullres_head(*args, **kw))
     for a, c in zip(first, second):
         assert torch.equal(a.cpu(), c.cpu())
 
 
 @pytest.fixture(scope="module")
 def tiny_model(dev):
-    from mdil_ss_amd.models.erfnet_RA_parallel import Net as Net_RAP
-    torch.manual_seed(0)
-    return Net_RAP([20, 20], 2, 1).to(dev).eval()
+    return HC.tiny_model(dev)
 
 
 def test_agrees_with_the_shipped_forward(dev, tiny_model):
@@ -343,7 +254,7 @@ def test_agrees_with_the_shipped_forward(dev, tiny_model):
     assert colour is None and tuple(label.shape) == (2,) + size
     w, b = (t.detach().cpu() for t in tiny_model.head_params(0))
     _, excluded = reference(feat.cpu().permute(0, 3, 1, 2), w, b, size)
-    check_labels(label.cpu(), want, excluded, "shipped path")
+    HC.check_labels(label.cpu(), want, excluded, "shipped path", HC.count_cap)
 
 
 def test_cli_end_to_end(dev, tiny_model, tmp_path):
@@ -355,7 +266,7 @@ def test_cli_end_to_end(dev, tiny_model, tmp_path):
     from mdil_ss_amd.dataset import ProceduralSeg
     from mdil_ss_amd.predict import default_palette
     ckpt, out, report_file = tmp_path / "checkpoint.pth.tar", tmp_path / "maps", tmp_path / "report.json"
-    torch.save({"state_dict": {"module." + k: v.cpu() for k, v in tiny_model.state_dict().items()}}, ckpt)
+    HC.save_checkpoint(tiny_model, ckpt)
     report = FR.main(FR.build_parser().parse_args(
         ["--state", str(ckpt), "--num-classes", "20", "20", "--task", "1", "--synthetic", "3", "--native-height", "96",
          "--native-width", "200", "--height", "64", "--width", "128", "--score", "--json", str(report_file),

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import head_cases as HC
 from tests import tsne_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -23,9 +24,7 @@ U = 2.0 ** -24
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "the latent-space path needs an MI355X"
-    import mdil_ss_amd  # noqa: F401
-    return torch.device("cuda", 0)
+    return HC.device("latent-space")
 
 
 @functools.lru_cache(maxsize=None)
@@ -322,9 +321,7 @@ def test_end_to_end_on_three_clusters(dev):
 # ------------------------------------------------------------------------------------ latents
 @pytest.fixture(scope="module")
 def tiny_model(dev):
-    from mdil_ss_amd.models.erfnet_RA_parallel import Net as Net_RAP
-    torch.manual_seed(0)
-    return Net_RAP([20, 20], 2, 1).to(dev).eval()
+    return HC.tiny_model(dev)
 
 
 def test_latents_are_the_models_own_tensors(dev, tiny_model):
@@ -357,7 +354,7 @@ def test_cli_end_to_end(dev, tiny_model, tmp_path, capsys):
 
     from mdil_ss_amd import latent as L
     ckpt = tmp_path / "model_best.pth.tar"
-    torch.save({"state_dict": {"module." + k: v.cpu() for k, v in tiny_model.state_dict().items()}}, ckpt)
+    HC.save_checkpoint(tiny_model, ckpt)
     base = ["--state", str(ckpt), "--num-classes", "20", "20", "--task", "0", "--synthetic", "1", "--height", "64",
             "--width", "128"]
     enc = base + ["--layer", "encoder", "--perplexity", "5", "--iterations", "60"]

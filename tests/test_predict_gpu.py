@@ -1,13 +1,11 @@
 """GPU: the fused output_conv + argmax kernel (mdil_ss_amd/ext/predict_head.hip) and the entry points
-over it (mdil_ss_amd/predict.py), against an fp64 reference on the CPU:
+over it (mdil_ss_amd/predict.py), against the fp64 reference of tests/head_cases.py:
 ``F.conv_transpose2d(x.double(), w.double(), b.double(), stride=2)``, then argmax and softmax.
 
-Which pixels may differ.  Two fp32 evaluations of a 17-term sum (bias + 16 products) differ from the
-exact value by at most gamma_17 * S each, gamma_17 = 17u / (1 - 17u), u = 2^-24,
-S = |b_c| + sum_ci |x_ci| |w_ci,c|; so the order of two classes can flip only where their exact
-margin is at most 2 * gamma_17 * S (S of the larger of the two).  A pixel whose fp64 top-2 margin
-is within that bound is excluded, every other pixel must match exactly, and the excluded share is
-asserted to stay at or under 0.1 % of each case."""
+Which pixels may differ.  A logit is a 17-term sum (bias + 16 products), so k = 17 in the near-tie
+rule of tests/head_cases.py: a pixel whose fp64 top-2 margin is within 2 * gamma_17 * S is excluded,
+every other pixel must match exactly, and the excluded share is asserted to stay at or under 0.1 %
+of each case."""
 import functools
 import glob
 import os
@@ -17,13 +15,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import head_cases as HC
+from tests.head_cases import CLASSES, SHAPES, nhwc, random_palette
+
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
-GAMMA17 = 17 * U / (1 - 17 * U)
+K = 17
 MAX_EXCLUDED = 1e-3
-CLASSES = (2, 20, 27, 32)
-SHAPES = ((1, 1, 1), (1, 9, 7), (2, 12, 20), (3, 16, 48))
 # Confidence: worst relative error against the fp64 softmax maximum measured on an MI355X over the
 # 16 cases below and the grid-stride case (non-excluded pixels): 6.967e-07, at nc 32, shape
 # (1, 9, 7); per case 2.8e-08 ... 7.0e-07 ("Predict").  Asserted at twice the worst.
@@ -33,38 +31,16 @@ CONF_RTOL = 2 * CONF_WORST_MEASURED
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "the prediction path needs an MI355X"
-    import mdil_ss_amd  # noqa: F401
-    return torch.device("cuda", 0)
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
+    return HC.device("prediction")
 
 
 @functools.lru_cache(maxsize=None)
 def case(nc, shape):
-    """Seeded inputs (as tests/test_hip_parity.py::test_fused_head_and_loss draws them) and their
-    fp64 reference, computed once and shared: x [N,16,H,W], w, b, label, confidence, excluded."""
-    N, H, W = shape
-    g = torch.Generator().manual_seed(10 * nc + H)
-    w = torch.randn(16, nc, 2, 2, generator=g) * 0.3
-    b = torch.randn(nc, generator=g) * 0.2
-    x = F.relu(torch.randn(N, 16, H, W, generator=g))
-    return (x, w, b) + reference(x, w, b)
-
-
-def reference(x, w, b):
-    """-> (label i64 [N,2H,2W], confidence f64, excluded bool) from fp64 logits."""
-    logits = F.conv_transpose2d(x.double(), w.double(), b.double(), stride=2)
-    S = F.conv_transpose2d(x.double().abs(), w.double().abs(), b.double().abs(), stride=2)
-    return (logits.max(1)[1], F.softmax(logits, 1).max(1)[0], near_tie(logits, S))
-
-
-def near_tie(logits, S):
-    top, idx = logits.topk(2, dim=1)
-    bound = 2 * GAMMA17 * S.gather(1, idx).max(1)[0]
-    return (top[:, 0] - top[:, 1]) <= bound
+    """The shared inputs of a case and their fp64 reference, computed once and never modified:
+    x [N,16,H,W], w, b, label i64 [N,2H,2W], confidence f64, excluded bool."""
+    x, w, b = HC.head_inputs(nc, shape)
+    logits, S = HC.head64(x, w, b)
+    return x, w, b, logits.max(1)[1], F.softmax(logits, 1).max(1)[0], HC.near_tie(logits, S, K)
 
 
 def run(dev, x, w, b, palette=None, want_confidence=False):
@@ -75,22 +51,13 @@ def run(dev, x, w, b, palette=None, want_confidence=False):
     return tuple(None if t is None else t.cpu() for t in out)
 
 
-def random_palette(nc):
-    return torch.randint(0, 256, (nc, 3), generator=torch.Generator().manual_seed(nc), dtype=torch.uint8)
-
-
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("nc", CLASSES)
 def test_labels_match_fp64_argmax(dev, nc, shape):
     x, w, b, ref, _, excluded = case(nc, shape)
-    share = excluded.double().mean().item()
-    print(f"nc {nc} shape {shape}: excluded {int(excluded.sum())} of {excluded.numel()} pixels")
-    assert share <= MAX_EXCLUDED, f"{share:.2%} of the pixels are fp32 near-ties: choose another seed"
     label, colour, conf = run(dev, x, w, b)
     assert colour is None and conf is None
-    assert label.dtype == torch.uint8 and tuple(label.shape) == tuple(ref.shape)
-    wrong = (label.long() != ref) & ~excluded
-    assert not wrong.any(), f"{int(wrong.sum())} of {wrong.numel()} labels differ from the fp64 argmax"
+    HC.check_labels(label, ref, excluded, f"nc {nc} shape {shape}", HC.share(MAX_EXCLUDED))
 
 
 def test_ties_go_to_the_lowest_class(dev):
@@ -140,28 +107,22 @@ def test_colour_is_the_palette_row_of_the_label(dev, nc, shape):
 
 
 def _raw_call(dev, x, w, b, pal, with_colour, with_conf):
-    """The C entry point on one sentinel-filled arena: [guard | label | guard | colour | guard |
-    confidence | guard].  -> (arena bytes on the host, offsets, sizes)."""
+    """The C entry point on one sentinel arena [guard | label | guard | colour | guard | confidence |
+    guard] -> the arena, read back."""
     from mdil_ss_amd import _predict_lib
     lib = _predict_lib.load()
     N, _, H, W = x.shape
     npx = N * 4 * H * W
-    G = 256
-    sizes = {"label": npx, "colour": 3 * npx, "confidence": 4 * npx}
-    off, pos = {}, G
-    for k in ("label", "colour", "confidence"):
-        off[k] = pos
-        pos = (pos + sizes[k] + G + 15) // 16 * 16
-    arena = torch.full((pos,), 0xA5, dtype=torch.uint8, device=dev)
+    arena = HC.Arena(dev, {"label": npx, "colour": 3 * npx, "confidence": 4 * npx})
     xd, wd, bd, pd = nhwc(x).to(dev), w.to(dev), b.to(dev), pal.to(dev)
-    base = arena.data_ptr()
     rc = lib.mdil_predict_head(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), N, H, W, w.shape[1], pd.data_ptr(),
-                               base + off["label"], base + off["colour"] if with_colour else None,
-                               base + off["confidence"] if with_conf else None,
+                               arena.ptr("label"), arena.ptr("colour") if with_colour else None,
+                               arena.ptr("confidence") if with_conf else None,
                                torch.cuda.current_stream().cuda_stream)
     assert rc == 0, lib.mdil_predict_last_error()
     torch.cuda.synchronize()
-    return arena.cpu(), off, sizes
+    arena.read()
+    return arena
 
 
 @pytest.mark.parametrize("shape", ((1, 1, 1), (1, 9, 7), (3, 16, 48)))
@@ -172,16 +133,12 @@ def test_null_outputs_and_guard_bands_stay_untouched(dev, shape):
     pal = random_palette(27)
     label = run(dev, x, w, b)[0].reshape(-1)
     for with_colour, with_conf in ((False, False), (True, True)):
-        arena, off, sizes = _raw_call(dev, x, w, b, pal, with_colour, with_conf)
-        written = torch.zeros(arena.numel(), dtype=torch.bool)
-        for k, on in (("label", True), ("colour", with_colour), ("confidence", with_conf)):
-            if on:
-                written[off[k]:off[k] + sizes[k]] = True
-        assert (arena[~written] == 0xA5).all(), (with_colour, with_conf)
-        assert torch.equal(arena[off["label"]:off["label"] + sizes["label"]], label)
+        arena = _raw_call(dev, x, w, b, pal, with_colour, with_conf)
+        on = (("label", True), ("colour", with_colour), ("confidence", with_conf))
+        arena.assert_untouched([k for k, given in on if given], (with_colour, with_conf))
+        assert torch.equal(arena.cut("label"), label)
         if with_colour:
-            got = arena[off["colour"]:off["colour"] + sizes["colour"]].reshape(-1, 3)
-            assert torch.equal(got, pal[label.long()])
+            assert torch.equal(arena.cut("colour").reshape(-1, 3), pal[label.long()])
 
 
 @pytest.mark.parametrize("shape", SHAPES)
@@ -205,11 +162,10 @@ def test_grid_stride_loop_past_the_grid_bound(dev):
     nc, shape = 2, (1, 513, 1023)
     assert shape[0] * shape[1] * shape[2] > 2048 * 256
     x, w, b, ref, ref_conf, excluded = case(nc, shape)
-    assert excluded.double().mean().item() <= MAX_EXCLUDED
     pal = random_palette(nc)
     label, colour, conf = run(dev, x, w, b, pal, True)
+    HC.check_labels(label, ref, excluded, f"nc {nc} shape {shape}", HC.share(MAX_EXCLUDED))
     keep = ~excluded
-    assert torch.equal(label.long()[keep], ref[keep])
     assert torch.equal(colour, pal[label.long()])
     rel = ((conf.double() - ref_conf).abs() / ref_conf)[keep]
     print(f"nc {nc} shape {shape}: confidence worst relative error {rel.max().item():.3e}")
@@ -218,9 +174,7 @@ def test_grid_stride_loop_past_the_grid_bound(dev):
 
 @pytest.fixture(scope="module")
 def tiny_model(dev):
-    from mdil_ss_amd.models.erfnet_RA_parallel import Net as Net_RAP
-    torch.manual_seed(0)
-    return Net_RAP([20, 20], 2, 1).to(dev).eval()
+    return HC.tiny_model(dev)
 
 
 def test_agrees_with_the_shipped_forward(dev, tiny_model):
@@ -236,14 +190,10 @@ def test_agrees_with_the_shipped_forward(dev, tiny_model):
     label, colour, conf = predict(tiny_model, images, 0)
     torch.cuda.synchronize()
     assert colour is None and conf is None and tuple(label.shape) == (2, 64, 128)
-    w, b = (t.detach().cpu().double() for t in tiny_model.head_params(0))
-    S = F.conv_transpose2d(feat.cpu().double().permute(0, 3, 1, 2).abs(), w.abs(), b.abs(), stride=2)
-    excluded = near_tie(logits.cpu().double(), S)
-    share = excluded.double().mean().item()
-    print(f"shipped path: excluded {int(excluded.sum())} of {excluded.numel()} pixels")
-    assert share <= MAX_EXCLUDED
-    wrong = (label.cpu().long() != logits.max(1)[1].cpu()) & ~excluded
-    assert not wrong.any(), f"{int(wrong.sum())} of {wrong.numel()} labels differ from the shipped path"
+    w, b = (t.detach().cpu() for t in tiny_model.head_params(0))
+    _, S = HC.head64(feat.cpu().permute(0, 3, 1, 2), w, b)
+    excluded = HC.near_tie(logits.cpu().double(), S, K)
+    HC.check_labels(label.cpu(), logits.max(1)[1].cpu(), excluded, "shipped path", HC.share(MAX_EXCLUDED))
 
 
 def test_side_stream_gives_the_same_bytes(dev):
@@ -252,10 +202,7 @@ def test_side_stream_gives_the_same_bytes(dev):
     args = (nhwc(x).to(dev), w.to(dev), b.to(dev), random_palette(27).to(dev), True)
     first = predict_head(*args)
     torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    with torch.cuda.stream(side):
-        second = predict_head(*args)
-    side.synchronize()
+    second = HC.side_stream(lambda: predict_head(*args))
     for a, c in zip(first, second):
         assert torch.equal(a.cpu().view(torch.uint8), c.cpu().view(torch.uint8))
 
@@ -267,7 +214,7 @@ def test_cli_end_to_end(dev, tiny_model, tmp_path):
     from mdil_ss_amd import predict as P
     from mdil_ss_amd.dataset import ProceduralSeg
     ckpt, out = tmp_path / "checkpoint.pth.tar", tmp_path / "maps"
-    torch.save({"state_dict": {"module." + k: v.cpu() for k, v in tiny_model.state_dict().items()}}, ckpt)
+    HC.save_checkpoint(tiny_model, ckpt)
     written = P.main(P.build_parser().parse_args(
         ["--state", str(ckpt), "--num-classes", "20", "20", "--task", "1", "--synthetic", "3", "--height", "64",
          "--width", "128", "--batch-size", "3", "--colour", "--confidence", "--out", str(out)]))

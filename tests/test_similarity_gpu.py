@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import head_cases as HC
 from tests import similarity_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -29,9 +30,7 @@ BLOCKS = ("sx", "sy", "gxx", "gyy", "gxy")
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "the similarity path needs an MI355X"
-    import mdil_ss_amd  # noqa: F401
-    return torch.device("cuda", 0)
+    return HC.device("similarity")
 
 
 def bound():
@@ -181,26 +180,7 @@ def test_device_refusals(dev):
 # ---------------------------------------------------------------------------------- end to end
 @pytest.fixture(scope="module")
 def models(dev):
-    """(teacher [20], student [20, 20] initialised from it and then perturbed), as tests/test_drift_gpu.py."""
-    from mdil_ss_amd.models.erfnet_RA_parallel import Net as Net_RAP
-    from oracle import fixtures as fx
-    from oracle import rap_oracle as O
-    torch.manual_seed(1)
-    teacher = Net_RAP([20], 1, 0)
-    t_sd = {k: v.clone() for k, v in teacher.state_dict().items()}
-    fx.perturb_bn(t_sd, 11)
-    teacher.load_state_dict(t_sd)
-    torch.manual_seed(0)
-    student = Net_RAP([20, 20], 2, 1)
-    s_sd = {k: v.clone() for k, v in student.state_dict().items()}
-    for k, v in O.student_init_from_teacher(t_sd, s_sd, 1).items():
-        s_sd[k].copy_(v)
-    student.load_state_dict(s_sd)
-    g = torch.Generator().manual_seed(7)
-    with torch.no_grad():
-        for p in student.parameters():
-            p.mul_(1 + 0.05 * torch.randn(p.shape, generator=g))
-    return teacher.to(dev).eval(), student.to(dev).eval()
+    return HC.teacher_student(dev)
 
 
 @pytest.fixture(scope="module")
@@ -261,7 +241,7 @@ def test_cli_end_to_end_in_both_modes(dev, models, tmp_path):
     from mdil_ss_amd import similarity as S
     teacher, student = models
     for model, name in ((teacher, "before.pth.tar"), (student, "after.pth.tar")):
-        torch.save({"state_dict": {"module." + k: v.cpu() for k, v in model.state_dict().items()}}, tmp_path / name)
+        HC.save_checkpoint(model, tmp_path / name)
     size = ["--synthetic", "2", "--height", "64", "--width", "128"]
     ckpt = ["--before", str(tmp_path / "before.pth.tar"), "--before-num-classes", "20", "--after",
             str(tmp_path / "after.pth.tar"), "--after-num-classes", "20", "20", "--task", "0"] + size
