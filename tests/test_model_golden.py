@@ -132,9 +132,9 @@ def test_step2_iteration_against_reference_golden(golden, sink):
         d_rows = Hh.digest_rows([delta])[0]
         scale = float(g_own[n].abs().max())
         want = ref[i, lin] + d_rows[lin]
-        want[0] = got[i, 0] if g_own[n].numel() > 4096 else want[0]     # (sums of large tensors cancel: samples only)
         tol = 1e-3 * np.abs(want) + 2e-4 * scale * np.where(np.arange(len(lin)) == 0, g_own[n].numel() ** 0.5, 1.0)
         bad = np.abs(got[i, lin] - want) > tol
+        bad[0] &= g_own[n].numel() <= 4096                               # (sums of large tensors cancel: samples only)
         assert not bad.any(), (n, int(bad.sum()), got[i, lin][bad][:4], want[bad][:4], scale)
         # norms: HIP against the oracle on the SAME gates (the reference's norm on other gates is not comparable)
         l2_o = float(g_hipgates[n].norm())
