@@ -1,0 +1,616 @@
+"""GPU: the label-audit kernels (mdil_ss_amd/ext/audit_head.hip) and the entry points over them
+(mdil_ss_amd/audit.py), against tests/audit_reference.py and the fp64 head of tests/head_cases.py.
+
+What is compared with what.  ``audit_head`` promises ``openset_head``'s chain of operations, so with
+thresholds of 0 its suggestion is ``predict_head``'s label: asserted bit for bit.  Independently every
+16-bit probability is held to its fp64 definition: q must lie between q_of(p64 (1 - r)) and
+q_of(p64 (1 + r)), r per case the larger of the logit bound 2 gamma_17 max S + 8 u (a logit within
+gamma_17 S moves a probability by at most twice that, relatively; 8 u for the exp2, the sum, the
+reciprocal and the product) and 4 x the worst relative distance of a plain float32 torch softmax from
+fp64 on the same case.  The test prints how far the kernel's q lie from the fp64 probability as a
+multiple of that float32 distance.  Everything after q is integer arithmetic and is asserted exactly,
+on the kernel's own maps: the thresholds come from its own count and qsum, the confident set of every
+pixel from its own q maps, and the suggestion must be the fp64-logit argmax over that set wherever the
+two largest logits of the set are not within 2 gamma_17 S of each other (tests/test_audit_cpu.py holds
+the number of such pixels under ``head_cases.count_cap`` on the reference alone; here the cap is
+asserted again for the kernel's sets)."""
+import functools
+import glob
+import json
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import audit_reference as R
+from tests import head_cases as HC
+from tests.head_cases import CLASSES, SHAPES, nhwc
+
+pytestmark = pytest.mark.gpu
+
+K = 17
+BIG = (3, 16, 48)
+SCALE = 8.0                                     # the trained regime: logits 8 times as far apart
+NPIX = (1, 3, 5, 1001, 1024)                    # 8 pixels per load: odd tails, a ragged and a whole size
+CROWD = ((1, 9, 7), (2, 12, 20), BIG)
+HEAD_WG, HEAD_BLOCKS = 256, 768                 # audit_head.hip: kHeadWG, kHeadMaxBlocks
+IGNORE, NONE = 255, 254
+SENTINEL = torch.tensor([0xA5] * 8, dtype=torch.uint8).view(torch.int64)
+
+
+@pytest.fixture(scope="module")
+def dev():
+    return HC.device("label-audit")
+
+
+def inputs(nc, shape, scale=1.0):
+    x, w, b = HC.head_inputs(nc, shape)
+    return x, (w * scale if scale != 1.0 else w), b
+
+
+def case_target(nc, shape):
+    return HC.make_target(nc, (shape[0], 2 * shape[1], 2 * shape[2]), IGNORE, seed=nc + shape[1])
+
+
+@functools.lru_cache(maxsize=None)
+def reference(nc, shape, scale=1.0):
+    """fp64 logits, S and probabilities; the float32 torch softmax's worst relative distance from them;
+    the relative bound r.  Computed once, never modified."""
+    x, w, b = inputs(nc, shape, scale)
+    logits, S = HC.head64(x, w, b)
+    p64 = R.probs64(logits)
+    p32 = F.softmax(F.conv_transpose2d(x, w, b, stride=2), 1).double()
+    rel32 = float(((p32 - p64).abs() / p64).max())
+    r = max(2 * HC.gamma(K) * float(S.max()) + 8 * HC.U, 4.0 * rel32)
+    return logits, S, p64, rel32, r
+
+
+def two_sweeps(dev, xd, wd, bd, target, ignore=IGNORE, none_id=NONE, want_q=False):
+    """Sweep 1, the thresholds of its counters, sweep 2 -> host tensors (and the device maps)."""
+    from mdil_ss_amd import audit as A
+    nc, N = wd.shape[1], xd.shape[0]
+    td = target.to(dev)
+    c1 = A.new_head_counters(nc, N, dev, ("count", "qsum", "bad_targets", "nonfinite"))
+    selfq, _ = A.audit_head(xd, wd, bd, td, ignore, q_class="given", none_id=none_id, counters=c1)
+    thr = A.thresholds(c1["count"].cpu(), c1["qsum"].cpu())
+    c2 = A.new_head_counters(nc, N, dev, ("count", "joint", "per_image", "bad_targets", "nonfinite"))
+    selfq2, suggest = A.audit_head(xd, wd, bd, td, ignore, thr, "given", none_id, c2, want_suggest=True)
+    out = dict(thr=thr, selfq=A.q_values(selfq.cpu()), suggest=suggest.cpu(), dselfq=selfq, dsuggest=suggest, dtarget=td,
+               sweep1={k: v.cpu() for k, v in c1.items()}, sweep2={k: v.cpu() for k, v in c2.items()}, args=(xd, wd, bd))
+    assert torch.equal(HC.as_bytes(selfq.cpu()), HC.as_bytes(selfq2.cpu()))
+    if want_q:
+        out["q"] = torch.stack([A.q_values(A.audit_head(xd, wd, bd, q_class=c)[0].cpu()) for c in range(nc)], 1)
+    return out
+
+
+def suggest_index(suggest, nc, none_id=NONE):
+    """The kernel's suggest map as the reference writes it: nc for "none"."""
+    s = suggest.long()
+    assert bool(((s < nc) | (s == none_id)).all())
+    return torch.where(s == none_id, torch.full_like(s, nc), s)
+
+
+def check_integer_contracts(run, target, nc, ignore=IGNORE, none_id=NONE, times=1, base=0):
+    """count, qsum, joint, per_image and bad_targets are the bincounts of the kernel's own maps."""
+    sidx = suggest_index(run["suggest"], nc, none_id)
+    count, qsum = R.count_qsum(run["selfq"], target, nc, ignore)
+    bad = int(((target.long() >= nc) & (target.long() != ignore)).sum())
+    s1, s2 = run["sweep1"], run["sweep2"]
+    assert torch.equal(s1["count"], count) and torch.equal(s1["qsum"], qsum) and int(s1["bad_targets"]) == bad
+    assert torch.equal(s2["count"] - base, times * count) and int(s2["bad_targets"]) - base == times * bad
+    assert torch.equal(s2["joint"] - base, times * R.joint_of(target, sidx, nc, ignore))
+    assert torch.equal(s2["per_image"] - base, times * R.per_image_of(target, sidx, nc, ignore))
+    assert int(s1["nonfinite"]) == 0 and int(s2["nonfinite"]) - base == 0
+    assert int((s2["joint"] - base).sum()) == times * int(count.sum())
+    invalid = ~R.valid_of(target, nc, ignore)
+    assert bool((run["selfq"][invalid] == 0).all())
+    return sidx
+
+
+@functools.lru_cache(maxsize=None)
+def device_run(nc, shape, scale=1.0):
+    """The two sweeps on case (nc, shape), one q map per class, the suggestions at thresholds of 0 and of
+    65536, and predict_head on the same inputs."""
+    from mdil_ss_amd import audit as A
+    dev = torch.device("cuda", 0)
+    x, w, b = inputs(nc, shape, scale)
+    xd, wd, bd = nhwc(x).to(dev), w.to(dev), b.to(dev)
+    target = case_target(nc, shape)
+    run = two_sweeps(dev, xd, wd, bd, target, want_q=True)
+    run["all"] = A.audit_head(xd, wd, bd, thr=[0] * nc, none_id=NONE, want_suggest=True)[1].cpu()
+    run["nobody"] = A.audit_head(xd, wd, bd, thr=[65536] * nc, none_id=NONE, want_suggest=True)[1].cpu()
+    run["plabel"] = HC.predict_labels(dev, x, w, b)
+    run["target"] = target
+    return run
+
+
+# ------------------------------------------------------------------------------------- (1) bits
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("nc", CLASSES)
+def test_suggestion_at_threshold_zero_is_predict_heads_label(dev, nc, shape):
+    run = device_run(nc, shape)
+    assert run["all"].dtype == torch.uint8 and tuple(run["all"].shape) == (shape[0], 2 * shape[1], 2 * shape[2])
+    assert torch.equal(run["all"], run["plabel"])
+    assert bool((run["nobody"] == NONE).all())
+    assert int(run["sweep1"]["nonfinite"]) == 0 and int(run["sweep2"]["nonfinite"]) == 0
+
+
+def test_an_infinite_feature_is_counted_and_enters_no_counter(dev):
+    from mdil_ss_amd import audit as A
+    nc, shape = 20, (2, 12, 20)
+    x, w, b = inputs(nc, shape)
+    xi = x.clone()
+    xi[1, 9, 5, 7] = float("inf")                                   # one feature: its four output pixels
+    clean = device_run(nc, shape)
+    target = clean["target"].clone()
+    target[1, 10:12, 14:16] = torch.tensor([[3, IGNORE], [nc, 5]], dtype=torch.uint8)
+    hit = torch.zeros(target.shape, dtype=torch.bool)
+    hit[1, 10:12, 14:16] = True
+    xd, wd, bd, td = nhwc(xi).to(dev), w.to(dev), b.to(dev), target.to(dev)
+    c = A.new_head_counters(nc, 2, dev)
+    selfq, suggest = A.audit_head(xd, wd, bd, td, IGNORE, clean["thr"], "given", NONE, c, want_suggest=True)
+    selfq, suggest = A.q_values(selfq.cpu()), suggest.cpu()
+    assert int(c["nonfinite"]) == 4 and bool((suggest[hit] == NONE).all()) and bool((selfq[hit] == 0).all())
+    assert torch.equal(suggest[~hit], clean["suggest"][~hit]) and torch.equal(selfq[~hit], clean["selfq"][~hit])
+    for cls in (0, 3, nc - 1):
+        qmap = A.q_values(A.audit_head(xd, wd, bd, q_class=cls)[0].cpu())
+        assert bool((qmap[hit] == 0).all()) and torch.equal(qmap[~hit], clean["q"][:, cls][~hit])
+    finite = ~hit
+    sidx = suggest_index(suggest, nc)
+    count, qsum = R.count_qsum(selfq, target, nc, IGNORE, finite)
+    assert torch.equal(c["count"].cpu(), count) and torch.equal(c["qsum"].cpu(), qsum)
+    assert torch.equal(c["joint"].cpu(), R.joint_of(target, sidx, nc, IGNORE, finite))
+    assert torch.equal(c["per_image"].cpu(), R.per_image_of(target, sidx, nc, IGNORE, finite))
+    assert int(count.sum()) == int(R.valid_of(target, nc, IGNORE).sum()) - 2        # the two valid pixels that were hit
+    assert int(c["bad_targets"]) == int(((target.long() >= nc) & (target != IGNORE)).sum())   # a property of the target
+
+
+# ---------------------------------------------------------------------------------- (2) fp64
+def check_q(nc, shape, scale):
+    run = device_run(nc, shape, scale)
+    logits, S, p64, rel32, r = reference(nc, shape, scale)
+    what = f"nc {nc} shape {shape} scale {scale}"
+    q = run["q"]
+    lo, hi = R.q_of(p64 * (1 - r)), R.q_of(p64 * (1 + r))
+    floor = q.double() / 65536.0
+    ceil = torch.where(q == 65535, torch.full_like(floor, float("inf")), (q.double() + 1) / 65536.0)
+    away = float((torch.maximum(floor - p64, p64 - ceil).clamp(min=0) / p64).max())
+    print(f"{what}: r {r:.3e} (float32 torch softmax {rel32:.3e}); the kernel's q are at least {away:.3e} away = "
+          f"{away / max(rel32, 1e-300):.2f} x float32 torch; {int((q != R.q_of(p64)).sum())} of {q.numel()} q differ from "
+          "the fp64 q")
+    assert bool(((q >= lo) & (q <= hi)).all()), what
+    target = run["target"]
+    assert torch.equal(run["selfq"], R.self_q(q, target, nc, IGNORE))          # the "given" map is the q maps' own
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("nc", CLASSES)
+def test_q_match_the_fp64_softmax(dev, nc, shape):
+    check_q(nc, shape, 1.0)
+
+
+@pytest.mark.parametrize("nc", CLASSES)
+def test_q_in_the_trained_regime(dev, nc):
+    check_q(nc, BIG, SCALE)
+    run = device_run(nc, BIG, SCALE)
+    assert torch.equal(run["all"], run["plabel"])
+
+
+# ------------------------------------------------------------------------------ (3) integers
+def check_integers(nc, shape, scale):
+    run = device_run(nc, shape, scale)
+    logits, S, p64, rel32, r = reference(nc, shape, scale)
+    target = run["target"]
+    what = f"nc {nc} shape {shape} scale {scale}"
+    sidx = check_integer_contracts(run, target, nc)
+    inside = R.confident(run["q"], run["thr"])                       # from the kernel's own q maps
+    excluded = R.near_tie_confident(logits, S, inside, HC.gamma(K))
+    HC.count_cap(excluded, what)
+    want = R.suggest_from(run["q"], run["thr"], logits)
+    wrong = (sidx != want) & ~excluded
+    assert not wrong.any(), f"{what}: {int(wrong.sum())} suggestions differ from the fp64 argmax over the confident set"
+    assert torch.equal(sidx == nc, inside.sum(1) == 0)               # "none" exactly where the set is empty
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("nc", CLASSES)
+def test_counters_and_suggestions_on_the_kernels_own_maps(dev, nc, shape):
+    check_integers(nc, shape, 1.0)
+
+
+@pytest.mark.parametrize("nc", CLASSES)
+def test_counters_and_suggestions_in_the_trained_regime(dev, nc):
+    check_integers(nc, BIG, SCALE)
+
+
+@pytest.mark.parametrize("nc", (2, 27))
+def test_counters_accumulate_and_keep_what_they_held(dev, nc):
+    from mdil_ss_amd import audit as A
+    run = device_run(nc, BIG)
+    target = run["target"]
+    xd, wd, bd = run["args"]
+    for base in (0, 7):
+        c = {k: v + base for k, v in A.new_head_counters(nc, BIG[0], dev).items()}
+        for times in (1, 2):
+            selfq, suggest = A.audit_head(xd, wd, bd, run["dtarget"], IGNORE, run["thr"], "given", NONE, c, want_suggest=True)
+            assert torch.equal(suggest.cpu(), run["suggest"])
+            again = dict(run, sweep2={k: v.cpu() for k, v in c.items()})
+            check_integer_contracts(again, target, nc, times=times, base=base)
+            assert torch.equal(c["qsum"].cpu() - base, times * run["sweep1"]["qsum"])
+
+
+def test_grid_stride_loop_past_the_grid_bound(dev):
+    """The grid is bounded at 768 work-groups of 256 feature pixels; 70 x 53 x 53 = 196,630 of them sends 22
+    pixels round the loop a second time, into a work-group whose per-image table holds another image."""
+    nc, shape = 2, (70, 53, 53)
+    assert 0 < shape[0] * shape[1] * shape[2] - HEAD_WG * HEAD_BLOCKS < 64
+    x, w, b = HC.draw(nc, shape, 5)
+    target = HC.make_target(nc, (shape[0], 2 * shape[1], 2 * shape[2]), IGNORE, seed=9)
+    run = two_sweeps(dev, nhwc(x).to(dev), w.to(dev), b.to(dev), target)
+    check_integer_contracts(run, target, nc)
+    assert int(run["sweep2"]["per_image"][69, :, 0].sum()) > 0
+
+
+# ------------------------------------------------------------------------------- (4) crowding
+@pytest.mark.parametrize("shape", CROWD)
+def test_crowded_counters(dev, shape):
+    """The inputs on which a merge inside the wave goes wrong: every lane in one class, lanes that alternate
+    between two classes (by column: both in every lane; by lane parity: neighbouring lanes differ), and an
+    image that is ignored altogether."""
+    nc = 20
+    N, H, W = shape
+    _, w, b = inputs(nc, shape)
+    w = w[:, :, :1, :1].expand(-1, -1, 2, 2).contiguous()           # one weight for the four parities
+    x = torch.zeros(N, 16, H, W)
+    x[:, :, :, 1::2] = 1.5                                          # two kinds of pixels
+    xd, wd, bd = nhwc(x).to(dev), w.to(dev), b.to(dev)
+    for pattern in ("one class", "by column", "by lane", "one image ignored"):
+        target = torch.full((N, 2 * H, 2 * W), 3, dtype=torch.uint8)
+        if pattern == "by column":
+            target[:, :, 1::2] = 11
+        elif pattern == "by lane":
+            target[:, :, 2::4] = 11
+            target[:, :, 3::4] = 11
+        elif pattern == "one image ignored":
+            target[N - 1] = IGNORE                                  # with one image: nothing is counted at all
+        run = two_sweeps(dev, xd, wd, bd, target)
+        check_integer_contracts(run, target, nc)
+        valid = int(R.valid_of(target, nc, IGNORE).sum())
+        assert int(run["sweep2"]["count"].sum()) == valid, pattern
+        if pattern == "one class":
+            assert int(run["sweep2"]["count"][3]) == 4 * N * H * W
+        if pattern == "one image ignored":
+            assert int(run["sweep2"]["per_image"][N - 1].sum()) == 0 and bool((run["selfq"][N - 1] == 0).all())
+
+
+# -------------------------------------------------------------------------- (5) planted noise
+def planted_case(nc, shape, seed):
+    """Features one-hot in the true class x 4, w = 2 delta(ci, c), bias 0: the true logit is 8, the others 0.
+    -> x, w, b, true [N,2H,2W], target (10 % flipped to another class, every class at least once)."""
+    N, H, W = shape
+    g = torch.Generator().manual_seed(seed)
+    true_f = torch.randint(0, nc, (N, H, W), generator=g)
+    x = 4.0 * F.one_hot(true_f, 16).permute(0, 3, 1, 2).float()
+    w = torch.zeros(16, nc, 2, 2)
+    for c in range(nc):
+        w[c, c] = 2.0
+    true = true_f.repeat_interleave(2, 1).repeat_interleave(2, 2)
+    flat = true.reshape(-1)
+    flips = torch.randperm(flat.numel(), generator=g)[:flat.numel() // 10]
+    new = (flat[flips] + 1 + torch.randint(0, nc - 1, (flips.numel(),), generator=g)) % nc
+    used = set()
+    for k in range(nc):                                             # every class receives a flip
+        j = next(i for i in range(flips.numel()) if i not in used and int(flat[flips[i]]) != k)
+        new[j] = k
+        used.add(j)
+    target = flat.clone()
+    target[flips] = new
+    assert bool((target[flips] != flat[flips]).all()) and set(new.tolist()) == set(range(nc))
+    return x, w, torch.zeros(nc), true, target.reshape(true.shape).to(torch.uint8)
+
+
+@pytest.mark.parametrize("nc", (2, 16))
+def test_planted_label_noise_is_found_exactly(dev, nc):
+    shape = (2, 12, 20)
+    x, w, b, true, target = planted_case(nc, shape, seed=nc)
+    run = two_sweeps(dev, nhwc(x).to(dev), w.to(dev), b.to(dev), target, ignore=-1)
+    sidx = check_integer_contracts(run, target, nc, ignore=-1)
+    planted = target.long() != true
+    assert int(planted.sum()) == target.numel() // 10
+    assert torch.equal(sidx, true)                                   # the true class everywhere
+    assert torch.equal(R.issues_of(target, sidx, nc, -1), planted)   # the issue set is exactly the planted set
+    flip_matrix = torch.bincount(target.long()[planted] * nc + true[planted], minlength=nc * nc).reshape(nc, nc)
+    joint = run["sweep2"]["joint"]
+    off = joint[:, :nc].clone()
+    off.fill_diagonal_(0)
+    assert torch.equal(off, flip_matrix) and int(joint[:, nc].sum()) == 0
+    assert int(run["sweep2"]["per_image"][:, :, 1].sum()) == int(planted.sum())
+    assert bool((flip_matrix.sum(1) > 0).all())                      # every class received a flip
+
+
+# ---------------------------------------------------------------------------------- (6) apply
+def mixed_max_q(nc):
+    return [(-1, 65535, 3000, 20000)[c % 4] for c in range(nc)]
+
+
+@pytest.mark.parametrize("npix", NPIX + (None,))
+@pytest.mark.parametrize("nc", (2, 20, 32))
+def test_apply_maps_and_counters(dev, nc, npix):
+    from mdil_ss_amd import audit as A
+    run = device_run(nc, BIG)
+    n = run["target"].numel() if npix is None else npix
+    ht, hs, hq = (run[k].reshape(-1)[:n] for k in ("target", "suggest", "selfq"))
+    dt, ds, dq = (run[k].reshape(-1)[:n] for k in ("dtarget", "dsuggest", "dselfq"))
+    for mode in A.MODES:
+        for max_q in ([-1] * nc, [65535] * nc, mixed_max_q(nc)):
+            want = R.apply_ref(ht, hs, hq, nc, IGNORE, NONE, mode, max_q, 250)
+            counters = A.new_apply_counters(nc, dev)
+            for times in (1, 2):
+                out, mask = A.audit_apply(dt, ds, dq, nc, max_q, mode, IGNORE, NONE, 250, counters, want_mask=True)
+                assert out.dtype == torch.uint8 and torch.equal(out.cpu(), want["out"]), (mode, max_q)
+                assert mask.dtype == torch.uint8 and torch.equal(mask.cpu(), want["mask"]), (mode, max_q)
+                assert torch.equal(counters["seen"].cpu(), times * want["seen"])
+                assert torch.equal(counters["acted"].cpu(), times * want["acted"])
+                assert int(counters["bad_targets"]) == times * want["bad_targets"]
+            if max_q[0] == -1 and max_q[1] == -1:
+                assert torch.equal(want["out"], ht) and int(want["acted"].sum()) == 0
+        if npix is None:
+            every = R.apply_ref(ht, hs, hq, nc, IGNORE, NONE, mode, [65535] * nc, 250)
+            issues = R.issues_of(run["target"], suggest_index(run["suggest"], nc), nc, IGNORE)
+            assert int(every["acted"].sum()) == int(issues.sum()) > 0 and every["bad_targets"] > 0
+            assert torch.equal(every["mask"].reshape(issues.shape) == 255, issues)
+    some = {"acted": torch.zeros(nc, nc, dtype=torch.int64, device=dev)}
+    out, mask = A.audit_apply(dt, ds, dq, nc, [65535] * nc, "relabel", IGNORE, NONE, counters=some, want_out=False,
+                              want_mask=True)
+    plain = R.apply_ref(ht, hs, hq, nc, IGNORE, NONE, "relabel", [65535] * nc, 255)
+    assert out is None and torch.equal(mask.cpu(), plain["mask"]) and torch.equal(some["acted"].cpu(), plain["acted"])
+
+
+# ---------------------------------------------------------------- (7) guard bands and refusals
+HEAD_OUTPUTS = ("qmap", "suggest", "count", "qsum", "joint", "per_image", "bad_targets", "nonfinite")
+
+
+def head_arena(dev, nc, shape):
+    N, H, W = shape
+    npx = N * 4 * H * W
+    return HC.Arena(dev, {"qmap": 2 * npx, "suggest": npx, "count": nc * 8, "qsum": nc * 8, "joint": nc * (nc + 1) * 8,
+                          "per_image": N * nc * 2 * 8, "bad_targets": 8, "nonfinite": 8})
+
+
+def raw_head(lib, run, shape, nc, p, target=True, thr=True, q_class=None, nc_arg=None):
+    xd, wd, bd = run["args"]
+    N, H, W = shape
+    thr_d = run["dthr"]
+    return lib.mdil_audit_head(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), N, H, W, nc if nc_arg is None else nc_arg,
+                               run["dtarget"].data_ptr() if target else None, IGNORE, thr_d.data_ptr() if thr else None,
+                               nc if q_class is None else q_class, NONE, p["qmap"], p["suggest"], p["count"], p["qsum"],
+                               p["joint"], p["per_image"], p["bad_targets"], p["nonfinite"],
+                               torch.cuda.current_stream().cuda_stream)
+
+
+def head_combinations(shape):
+    if shape == (1, 9, 7):                                          # every NULL / non-NULL combination
+        return [tuple(k for i, k in enumerate(HEAD_OUTPUTS) if mask >> i & 1) for mask in range(1, 256)]
+    return [(k,) for k in HEAD_OUTPUTS] + [("count", "qsum"), ("suggest", "joint", "per_image"), HEAD_OUTPUTS]
+
+
+@pytest.mark.parametrize("shape", ((1, 1, 1), (1, 9, 7), BIG))
+def test_head_null_outputs_and_guard_bands_stay_untouched(dev, shape):
+    """What was not given keeps its sentinel bytes, and so do the guard bands.  The counters are ADDED to:
+    they start from the sentinel 0xA5A5A5A5A5A5A5A5."""
+    from mdil_ss_amd import _audit_lib
+    lib = _audit_lib.load()
+    nc = 27
+    run = dict(device_run(nc, shape))
+    run["dthr"] = torch.tensor(run["thr"], dtype=torch.int32).to(dev)
+    bad = int(run["sweep2"]["bad_targets"])
+    want = {"count": run["sweep2"]["count"], "qsum": run["sweep1"]["qsum"], "joint": run["sweep2"]["joint"],
+            "per_image": run["sweep2"]["per_image"]}
+    for given in head_combinations(shape):
+        arena = head_arena(dev, nc, shape)
+        p = {k: (arena.ptr(k) if k in given else None) for k in HEAD_OUTPUTS}
+        assert raw_head(lib, run, shape, nc, p) == 0, lib.mdil_audit_last_error()
+        torch.cuda.synchronize()
+        arena.read()
+        written = [k for k in given if k != "nonfinite" and (k != "bad_targets" or bad)]   # finite inputs: never touched
+        arena.assert_untouched(written, given)
+        if "qmap" in given:
+            assert torch.equal(arena.cut("qmap").view(torch.int16).long() & 0xffff, run["selfq"].reshape(-1)), given
+        if "suggest" in given:
+            assert torch.equal(arena.cut("suggest"), run["suggest"].reshape(-1)), given
+        for k, v in want.items():
+            if k in given:
+                assert torch.equal(arena.cut(k).view(torch.int64) - SENTINEL, v.reshape(-1)), (k, given)
+        if "bad_targets" in given and bad:
+            assert int(arena.cut("bad_targets").view(torch.int64) - SENTINEL) == bad
+
+
+def test_head_refusals_leave_everything_untouched(dev):
+    from mdil_ss_amd import _audit_lib
+    lib = _audit_lib.load()
+    nc, shape = 27, (1, 9, 7)
+    run = dict(device_run(nc, shape))
+    run["dthr"] = torch.tensor(run["thr"], dtype=torch.int32).to(dev)
+    arena = head_arena(dev, nc, shape)
+    every = {k: arena.ptr(k) for k in HEAD_OUTPUTS}
+    none = {k: None for k in HEAD_OUTPUTS}
+    refused = [
+        (dict(every), dict(target=False), b"need a target"),
+        (dict(none, count=every["count"]), dict(target=False), b"need a target"),
+        (dict(none, qmap=every["qmap"]), dict(target=False), b"q_class=27"),
+        (dict(every), dict(thr=False), b"need thr"),
+        (dict(none, suggest=every["suggest"]), dict(thr=False), b"need thr"),
+        (dict(none, per_image=every["per_image"]), dict(thr=False), b"need thr"),
+        (dict(every), dict(q_class=28), b"q_class=28"),
+        (dict(every), dict(nc_arg=33), b"nc=33"),
+        (dict(every), dict(nc_arg=1), b"nc=1"),
+        (dict(none), dict(), b"nothing to write"),
+        (dict(every, qmap=every["qmap"] + 2), dict(), b"alignment"),
+        (dict(every, suggest=every["suggest"] + 1), dict(), b"alignment"),
+        (dict(every, joint=every["joint"] + 4), dict(), b"alignment"),
+    ]
+    for p, kw, text in refused:
+        assert raw_head(lib, run, shape, nc, p, **kw) == -1, (kw, text)
+        assert text in lib.mdil_audit_last_error(), (text, lib.mdil_audit_last_error())
+    xd, wd, bd = run["args"]
+    rc = lib.mdil_audit_head(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), 1 << 20, 1 << 10, 1 << 10, nc,
+                             run["dtarget"].data_ptr(), IGNORE, run["dthr"].data_ptr(), nc, NONE, *every.values(), None)
+    assert rc == -1 and b"too large" in lib.mdil_audit_last_error()
+    torch.cuda.synchronize()
+    arena.read()
+    arena.assert_untouched([])
+
+
+@pytest.mark.parametrize("npix", (5, 1001, 1024))
+def test_apply_null_outputs_refusals_and_guard_bands(dev, npix):
+    from mdil_ss_amd import _audit_lib
+    lib = _audit_lib.load()
+    nc = 20
+    run = device_run(nc, BIG)
+    dt, ds, dq = (run[k].reshape(-1) for k in ("dtarget", "dsuggest", "dselfq"))
+    ht, hs, hq = (run[k].reshape(-1)[:npix] for k in ("target", "suggest", "selfq"))
+    max_q = mixed_max_q(nc)
+    dmax = torch.tensor(max_q, dtype=torch.int32).to(dev)
+    want = R.apply_ref(ht, hs, hq, nc, IGNORE, NONE, "relabel", max_q, 250)
+    sizes = {"out": npix, "mask": npix, "seen": nc * 8, "acted": nc * nc * 8, "bad_targets": 8}
+
+    def call(p, n=npix, mode=1, nc_arg=nc):
+        return lib.mdil_audit_apply(dt.data_ptr(), ds.data_ptr(), dq.data_ptr(), n, nc_arg, IGNORE, NONE, mode,
+                                    dmax.data_ptr(), 250, p["out"], p["mask"], p["seen"], p["acted"], p["bad_targets"],
+                                    torch.cuda.current_stream().cuda_stream)
+
+    combos = [tuple(k for i, k in enumerate(sizes) if m >> i & 1) for m in range(1, 32)]
+    for given in combos:
+        arena = HC.Arena(dev, sizes)
+        p = {k: (arena.ptr(k) if k in given else None) for k in sizes}
+        assert call(p) == 0, lib.mdil_audit_last_error()
+        torch.cuda.synchronize()
+        arena.read()
+        arena.assert_untouched([k for k in given if k != "bad_targets" or want["bad_targets"]], given)
+        for k in ("out", "mask"):
+            if k in given:
+                assert torch.equal(arena.cut(k), want[k]), (k, given)
+        for k in ("seen", "acted"):
+            if k in given:
+                assert torch.equal(arena.cut(k).view(torch.int64) - SENTINEL, want[k].reshape(-1)), (k, given)
+    arena = HC.Arena(dev, sizes)
+    every = {k: arena.ptr(k) for k in sizes}
+    for p, kw, text in ((dict.fromkeys(sizes), {}, b"nothing to write"), (every, dict(n=0), b"bad argument"),
+                        (every, dict(mode=2), b"mode=2"), (every, dict(nc_arg=33), b"nc=33"),
+                        (dict(every, out=every["out"] + 4), {}, b"alignment")):
+        assert call(p, **kw) == -1 and text in lib.mdil_audit_last_error(), text
+    torch.cuda.synchronize()
+    arena.read()
+    arena.assert_untouched([])
+
+
+def test_side_stream_gives_the_same_bytes(dev):
+    from mdil_ss_amd import audit as A
+    nc = 27
+    run = device_run(nc, BIG)
+    xd, wd, bd = run["args"]
+
+    def everything():
+        c = A.new_head_counters(nc, BIG[0], dev)
+        selfq, suggest = A.audit_head(xd, wd, bd, run["dtarget"], IGNORE, run["thr"], "given", NONE, c, want_suggest=True)
+        a = A.new_apply_counters(nc, dev)
+        out, mask = A.audit_apply(run["dtarget"], suggest, selfq, nc, mixed_max_q(nc), "relabel", IGNORE, NONE, 250, a,
+                                  want_mask=True)
+        return [selfq, suggest, out, mask] + [c[k] for k in A.HEAD_COUNTERS] + [a[k] for k in A.APPLY_COUNTERS]
+
+    first = everything()
+    torch.cuda.synchronize()
+    second = HC.side_stream(everything)
+    for a, c in zip(first, second):
+        assert torch.equal(HC.as_bytes(a.cpu()), HC.as_bytes(c.cpu()))
+    assert torch.equal(first[1].cpu(), run["suggest"])
+
+
+# ----------------------------------------------------------------------------- (8) end to end
+@pytest.fixture(scope="module")
+def tiny_model(dev):
+    return HC.tiny_model(dev)
+
+
+@pytest.fixture(scope="module")
+def checkpoint(tiny_model, tmp_path_factory):
+    path = tmp_path_factory.mktemp("audit") / "checkpoint.pth.tar"
+    HC.save_checkpoint(tiny_model, path)
+    return str(path)
+
+
+CLI = ["--num-classes", "20", "20", "--task", "1", "--synthetic", "2", "--height", "64", "--width", "128",
+       "--batch-size", "2"]
+
+
+def synthetic(dev, n, task):
+    from mdil_ss_amd.dataset import ProceduralSeg
+    ds = ProceduralSeg(n, 64, 128, 20, seed=12 + task, domain=task)
+    return (torch.stack([ds[i][0] for i in range(n)]).to(dev),
+            torch.stack([ds[i][1][0] for i in range(n)]).to(torch.uint8))
+
+
+@pytest.mark.parametrize("layout, mode", (("BDD", "prune"), ("cityscapes", "relabel")))
+def test_cli_report_issue_maps_and_cleaned_tree(dev, tiny_model, checkpoint, tmp_path, layout, mode):
+    import numpy as np
+    from PIL import Image
+    from mdil_ss_amd import audit as A
+    from mdil_ss_amd import dataset as D
+    report_file, out, root = tmp_path / "report.json", tmp_path / "maps", tmp_path / "clean"
+    A.main(A.build_parser().parse_args(["--state", checkpoint] + CLI + [
+        "--json", str(report_file), "--out", str(out), "--clean-root", str(root), "--layout", layout, "--mode", mode,
+        "--top", "5"]))
+    with open(report_file) as f:
+        saved = json.load(f)
+    images, target = synthetic(dev, 2, 1)
+    labelled = int((target != 19).sum())
+    joint = torch.tensor(saved["confident_joint"])
+    assert tuple(joint.shape) == (20, 21) and int(joint.sum()) == labelled == saved["labelled_pixels"]
+    assert saved["images"] == 2 and saved["nonfinite"] == 0 and saved["bad_targets"] == 0 and saved["ignore_index"] == 19
+    # the same figures from the meter, batch by batch
+    meter = A.LabelAuditor(20, 19)
+    meter.fit(tiny_model, images, 1, target=target.to(dev))
+    thr = meter.thresholds()
+    assert saved["thr"] == thr
+    selfq, suggest = meter.audit(tiny_model, images, 1, target=target.to(dev))
+    c = meter.counters()
+    assert torch.equal(c["joint"], joint) and saved["count"] == c["count"].tolist()
+    rep = A.confident_joint_report(c["joint"], c["count"], 5)
+    assert saved["calibrated_joint"] == rep["calibrated_joint"] and saved["top_pairs"] == rep["top_pairs"]
+    assert saved["noise_given"] == rep["noise_given"] and saved["estimated_issues"] == rep["estimated_issues"]
+    assert saved["top_images"] == A.top_images(c["per_image"], ["synthetic_0000", "synthetic_0001"], 5)
+    sidx = suggest_index(suggest.cpu(), 20, 255)
+    issues = R.issues_of(target, sidx, 20, 19)
+    assert saved["confident_issues"] == int(issues.sum()) == saved["acted_pixels"]
+    # the issue maps
+    assert len(glob.glob(str(out / "*_issues.png"))) == 2
+    from mdil_ss_amd.predict import default_palette
+    palette = default_palette(20)
+    for i in range(2):
+        with Image.open(out / f"synthetic_{i:04d}_issues.png") as im:
+            got = torch.from_numpy(np.array(im.convert("RGB")))
+        want = torch.where(issues[i].unsqueeze(2), palette[sidx[i].clamp(max=19)], torch.full((1, 3), 128, dtype=torch.uint8))
+        assert torch.equal(got, want)
+    # the cleaned tree, opened by the layout's own dataset class
+    ds = (D.BDD100k if layout == "BDD" else D.cityscapes)(str(root), subset="val")
+    assert len(ds) == 2 and len(ds.filenamesGt) == 2
+    for i in range(2):
+        image, label = ds[i]
+        assert image.size == (128, 64)
+        got = torch.from_numpy(np.array(label))
+        kept = torch.where(target[i] == 19, torch.tensor(255, dtype=torch.uint8), target[i])
+        acted = sidx[i].to(torch.uint8) if mode == "relabel" else torch.full_like(kept, 255)
+        acted = torch.where(acted == 19, torch.full_like(acted, 255), acted)
+        assert torch.equal(got, torch.where(issues[i], acted, kept))
+
+
+def test_cli_fit_then_thresholds(dev, checkpoint, tmp_path):
+    from mdil_ss_amd import audit as A
+    fit_file, report_file = tmp_path / "thr.json", tmp_path / "report.json"
+    fitted = A.main(A.build_parser().parse_args(["--state", checkpoint] + CLI + ["--fit", str(fit_file)]))
+    assert "confident_joint" not in fitted and len(fitted["thr"]) == 20
+    both = A.main(A.build_parser().parse_args(["--state", checkpoint] + CLI + ["--json", str(report_file)]))
+    again = A.main(A.build_parser().parse_args(["--state", checkpoint] + CLI + ["--thresholds", str(fit_file), "--json",
+                                                                                str(report_file)]))
+    assert again["thr"] == fitted["thr"] == both["thr"] and again["confident_joint"] == both["confident_joint"]
+    assert again["thresholds_from"] == str(fit_file) and "fit_count" not in again
