@@ -12,6 +12,7 @@
 //   route           vote, wave_sum, shape_ok, workspace_ok (its own per-image fold; calib_head's chain and forms at T = 1)
 //   refine          vote, stage_head, scoring_ok (logits4's chain for the one parity a lane owns)
 //   audit           vote, shape_ok, ignore_ok (openset_head's Wp staging and chain; its own helpers live in audit_head.hip)
+//   acquire         vote, shape_ok, ignore_ok (route_head's Wp staging and chain; its own helpers live in acquire_head.hip)
 // calib_head.hip forms its logits per parity from its own Wp[a*2+b][c][ci] staging, not through
 // logits4 (another LDS layout, the same chain), and keeps its DPP sums.
 #pragma once
