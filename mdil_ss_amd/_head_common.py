@@ -1,8 +1,10 @@
 """What the head drivers share (predict.py, fullres.py, ensemble.py and, with _report_common.py on
-top, drift.py and calibrate.py; latent.py and similarity.py take the loader and the parser): the
-argument checks of their ``*_head`` entry points -- each takes the entry point's name, so every
-message reads as it always did -- the checkpoint loader, the byte batch -> image tensor step, the
-bounded PNG writer and the score report of the inference command lines."""
+top, drift.py, calibrate.py, boundary.py, pseudo.py, route.py, segments.py, refine.py, significance.py,
+openset.py, audit.py and acquire.py; latent.py and similarity.py take the loader and the parser): the
+argument checks of their entry points -- each takes the entry point's name, so every message reads
+as it always did -- the 16-bit map, threshold and counter helpers of the map add-ons (pseudo,
+openset, audit, acquire), the checkpoint loader, the image folder -> image tensor steps, the bounded
+PNG writer and the score report of the inference command lines."""
 import json
 import os
 from argparse import ArgumentParser
@@ -42,10 +44,17 @@ def check_params(fn, w, b, x=None):
     return w.shape[1]
 
 
-def check_classes(fn, lib, nc, x, w, b, what="features"):
-    """The class range of the binding module ``lib``, then weight and bias on ``x``'s device."""
+def check_nc(fn, lib, nc):
+    """-> ``nc`` as an int within the class range of the binding module ``lib``."""
+    nc = int(nc)
     if not lib.MIN_CLASSES <= nc <= lib.MAX_CLASSES:
         raise RuntimeError(f"mdil {fn}: {nc} classes (supported: {lib.MIN_CLASSES} to {lib.MAX_CLASSES})")
+    return nc
+
+
+def check_classes(fn, lib, nc, x, w, b, what="features"):
+    """``check_nc``, then weight and bias on ``x``'s device."""
+    check_nc(fn, lib, nc)
     if w.device != x.device or b.device != x.device:
         raise RuntimeError(f"mdil {fn}: {what} on {x.device}, weight on {w.device}, bias on {b.device}")
 
@@ -91,6 +100,49 @@ def check_ignore_index(fn, ignore_index):
         raise RuntimeError(f"mdil {fn}: ignore_index {ignore_index} outside [-1, 255]")
 
 
+def check_id(fn, name, v):
+    """-> the byte ``v`` that a map is to hold (``name``: "drop_id", "none_id" ...)."""
+    if not 0 <= int(v) <= 255:
+        raise RuntimeError(f"mdil {fn}: {name} {v} outside [0, 255]")
+    return int(v)
+
+
+# ------------------------------------------------------------- the map add-ons' 16-bit maps and counters
+def q_values(qmap):
+    """A stored 16-bit map as int64 (uint16 tensors support few operations)."""
+    return qmap.view(torch.int16).to(torch.int64) & 0xffff
+
+
+def check_q_thresholds(fn, thr, nc, q_one, clause):
+    """-> the thresholds as a list of nc ints in [0, q_one]; ``clause`` says what a threshold decides."""
+    try:
+        t = [int(v) for v in (thr.tolist() if isinstance(thr, torch.Tensor) else thr)]
+    except (TypeError, ValueError):
+        raise RuntimeError(f"mdil {fn}: thr must be {nc} integers, got {thr!r}") from None
+    if len(t) != nc or any(v < 0 or v > q_one for v in t):
+        raise RuntimeError(f"mdil {fn}: thr must be {nc} integers in [0, {q_one}] ({clause}), got {t}")
+    return t
+
+
+def device_ints(fn, path, values, name, nc, dev, lo, hi):
+    """nc ints in [lo, hi] or an int32 [nc] device tensor (taken as it is) -> the device tensor."""
+    if isinstance(values, torch.Tensor) and values.is_cuda:
+        check_tables(fn, path, dev, torch.int32, ((values, name, (nc,)),))
+        return values
+    try:
+        v = [int(t) for t in (values.tolist() if isinstance(values, torch.Tensor) else values)]
+    except (TypeError, ValueError):
+        raise RuntimeError(f"mdil {fn}: {name} must be {nc} integers, got {values!r}") from None
+    if len(v) != nc or any(t < lo or t > hi for t in v):
+        raise RuntimeError(f"mdil {fn}: {name} must be {nc} integers in [{lo}, {hi}], got {v}")
+    return torch.tensor(v, dtype=torch.int32).to(dev)
+
+
+def zero_counters(shapes, dev, names=None):
+    """{name: zeroed int64 tensor of ``shapes[name]`` on ``dev``} over ``names`` (default: every shape)."""
+    return {k: torch.zeros(shapes[k], dtype=torch.int64, device=dev) for k in (shapes if names is None else names)}
+
+
 # -------------------------------------------------------------------------------- command lines
 class RefusingParser(ArgumentParser):
     """An ArgumentParser whose ``parse_args`` also runs ``refusals(args)`` and reports its
@@ -129,6 +181,16 @@ def image_batch(arrays, dev):
     """uint8 [h,w,3] arrays -> f32 [n,3,h,w] in [0, 1] on the device (the bytes cross the bus)."""
     u8 = torch.from_numpy(np.stack(arrays)).to(dev)
     return u8.permute(0, 3, 1, 2).to(torch.float32).div_(255.0)
+
+
+def image_batches(args, pool, dev):
+    """The images under ``--images`` (predict.py's reader: sorted, unique stems, resized to ``--height`` x
+    ``--width`` on ``pool``) -> (stems, images f32 [n,3,H,W] on the device) per batch of ``--batch-size``."""
+    from . import predict as P
+    files, stems = P._image_files(args.images)
+    for i in range(0, len(files), args.batch_size):
+        arrs = list(pool.map(lambda f: P._load_resized(f, args.height, args.width), files[i:i + args.batch_size]))
+        yield stems[i:i + args.batch_size], image_batch(arrs, dev)
 
 
 def _save_png(arr, path):

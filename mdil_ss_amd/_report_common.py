@@ -1,8 +1,10 @@
-"""What the report drivers (drift.py, calibrate.py, similarity.py) share on top of _head_common.py:
-the network-size batch feeder, the counter and workspace checks of ``drift_head`` / ``calib_head``,
-the workspace, source and bad-target steps of their meters, and the flags and refusals of their
-command lines.  Plain functions; each takes the caller's name where a message carries it,
-so every message reads as it always did."""
+"""What the report drivers (drift.py, calibrate.py, similarity.py, boundary.py, pseudo.py, route.py,
+segments.py, refine.py, significance.py, openset.py, audit.py, acquire.py) share on top of
+_head_common.py: the network-size batch feeders (a dataset, or a folder of images), the counter and
+workspace checks of the entry points, the workspace, source and bad-target steps of the meters, the
+label tree that audit and acquire write, and the flags and refusals of the command lines.  Plain
+functions; each takes the caller's name where a message carries it, so every message reads as it
+always did."""
 import os
 
 import torch
@@ -97,6 +99,44 @@ def batches(args, nc, dev, score=True, unique_stems=False):
         img, lab, params = (torch.stack([it[k] for it in items]).to(dev) for k in range(3))
         images, labels = ops.augment_batch(img, lab, params, nc)       # no flip, no shift; 255 -> nc - 1
         yield stems[i:i + len(items)], images, labels[:, 0].to(torch.uint8).contiguous() if score else None
+
+
+def image_or_dataset_batches(args, nc, pool, dev, score=True, unique_stems=False):
+    """``--images DIR`` (no targets) or ``batches``.  -> (stems, images f32 [n,3,H,W], target u8 [n,H,W] or
+    None) per batch, on the device."""
+    if args.images:
+        for stems, images in hc.image_batches(args, pool, dev):
+            yield stems, images, None
+        return
+    yield from batches(args, nc, dev, score=score, unique_stems=unique_stems)
+
+
+def source_name(args):
+    """What a report calls its source of images."""
+    return "images" if getattr(args, "images", None) else "synthetic" if args.synthetic else args.dataset
+
+
+def plan_label_tree(args, root):
+    """The folders of a label tree under ``root`` (``audit --clean-root``, ``acquire --out-root``), laid out
+    as ``--layout`` says, and the label file of every image, in the order of the batches.  A dataset's
+    images are linked (``pseudo.plan_tree``); procedural images have no files, so they are written beside
+    their labels.  -> (labels' folder, label names, images' folder or None)"""
+    from argparse import Namespace
+    from . import pseudo as P
+    img_dir, lab_dir = P.LAYOUTS[args.layout]
+    if args.synthetic:
+        images = os.path.join(root, img_dir, args.subset)
+        labels = os.path.join(root, lab_dir, args.subset)
+        os.makedirs(images, exist_ok=True)
+        os.makedirs(labels, exist_ok=True)
+        stems = [f"synthetic_{j:04d}" for j in range(args.synthetic)]
+        return labels, [P.label_name(args.layout, s) for s in stems], images
+    from .dataset import open_dataset
+    ds = open_dataset(args.dataset, args.subset, args, augment=False)
+    base = getattr(ds, "base", ds)
+    plan = Namespace(images=base.images_root, layout=args.layout, out_root=root, subset=args.subset)
+    labels, names = P.plan_tree(plan, base.filenames)
+    return labels, names, None
 
 
 def add_data_flags(p, dataset_help=None, synthetic_help="N procedural images instead of a dataset"):

@@ -28,7 +28,6 @@ of RIPU's sliding (2k+1)^2 neighbourhood, which is not built.  No retraining on 
 import json
 import math
 import os
-from argparse import Namespace
 
 import numpy as np
 import torch
@@ -49,17 +48,12 @@ MASK_SELECTED, MASK_KEPT, MASK_FILLED = 255, 128, 64
 _M64 = (1 << 64) - 1
 
 
-def q_values(qmap):
-    """A stored q map as int64 (uint16 tensors support few operations)."""
-    return qmap.view(torch.int16).to(torch.int64) & 0xffff
+q_values = hc.q_values                          # a stored q map as int64
+check_id = hc.check_id
 
 
 def check_nc(fn, nc):
-    nc = int(nc)
-    if not _acquire_lib.MIN_CLASSES <= nc <= _acquire_lib.MAX_CLASSES:
-        raise RuntimeError(f"mdil {fn}: {nc} classes (supported: {_acquire_lib.MIN_CLASSES} to "
-                           f"{_acquire_lib.MAX_CLASSES})")
-    return nc
+    return hc.check_nc(fn, _acquire_lib, nc)
 
 
 def check_tile(fn, tile):
@@ -80,12 +74,6 @@ def check_kind(fn, kind):
     return KINDS.index(kind)
 
 
-def check_id(fn, name, v):
-    if not 0 <= int(v) <= 255:
-        raise RuntimeError(f"mdil {fn}: {name} {v} outside [0, 255]")
-    return int(v)
-
-
 def tile_grid(size, tile):
     """Tiles of ``tile`` over a label grid of ``size`` = (Hl, Wl) -> (Ty, Tx); the last ones may be ragged."""
     return -(-int(size[0]) // tile[0]), -(-int(size[1]) // tile[1])
@@ -101,8 +89,7 @@ def apply_counter_shapes(nc):
 
 
 def new_apply_counters(nc, dev, names=APPLY_COUNTERS):
-    shapes = apply_counter_shapes(nc)
-    return {k: torch.zeros(shapes[k], dtype=torch.int64, device=dev) for k in names}
+    return hc.zero_counters(apply_counter_shapes(nc), dev, names)
 
 
 def new_tiles(N, size, tile, nc, dev):
@@ -299,40 +286,9 @@ def tile_boxes(size, tile):
 
 
 # ------------------------------------------------------------------------------------------ CLI
-def _source_name(args):
-    return "images" if args.images else "synthetic" if args.synthetic else args.dataset
-
-
-def _batches(args, nc, pool, dev):
-    """-> (stems, images f32 [n,3,H,W], target u8 [n,H,W] or None) per batch, on the device."""
-    if args.images:
-        from . import predict as P
-        files, stems = P._image_files(args.images)
-        for i in range(0, len(files), args.batch_size):
-            arrs = list(pool.map(lambda f: P._load_resized(f, args.height, args.width), files[i:i + args.batch_size]))
-            yield stems[i:i + args.batch_size], hc.image_batch(arrs, dev), None
-        return
-    yield from rc.batches(args, nc, dev, score=True, unique_stems=True)
-
-
 def plan_label_tree(args):
-    """The folders of ``--out-root`` and the label file of every image, in the order of the batches
-    (``audit.plan_clean_tree``'s rule).  -> (labels' folder, label names, images' folder or None)"""
-    from . import pseudo as P
-    img_dir, lab_dir = P.LAYOUTS[args.layout]
-    if args.synthetic:
-        images = os.path.join(args.out_root, img_dir, args.subset)
-        labels = os.path.join(args.out_root, lab_dir, args.subset)
-        os.makedirs(images, exist_ok=True)
-        os.makedirs(labels, exist_ok=True)
-        stems = [f"synthetic_{j:04d}" for j in range(args.synthetic)]
-        return labels, [P.label_name(args.layout, s) for s in stems], images
-    from .dataset import open_dataset
-    ds = open_dataset(args.dataset, args.subset, args, augment=False)
-    base = getattr(ds, "base", ds)
-    plan = Namespace(images=base.images_root, layout=args.layout, out_root=args.out_root, subset=args.subset)
-    labels, names = P.plan_tree(plan, base.filenames)
-    return labels, names, None
+    """The label tree of ``--out-root`` -> (labels' folder, label names, images' folder or None)."""
+    return rc.plan_label_tree(args, args.out_root)
 
 
 def _read_labels(root, layout, subset, names, size, what):
@@ -399,7 +355,7 @@ def main(args):
     # ---- pass 1: the tile table of every image, kept on the host
     tables, stems, given = [], [], torch.zeros(nc, dtype=torch.int64, device=dev)
     with hc.png_pool() as pool:
-        for s, images, target in _batches(args, nc, pool, dev):
+        for s, images, target in rc.image_or_dataset_batches(args, nc, pool, dev, unique_stems=True):
             if tuple(images.shape[2:]) != size:
                 raise RuntimeError(f"images of {tuple(images.shape[2:])}, expected {size}")
             t = new_tiles(images.shape[0], size, tile, nc, dev)
@@ -449,7 +405,7 @@ def main(args):
         live = torch.from_numpy(table[:, 0].numpy() > 0)
         hist_all, hist_sel = table[:, FIELDS:].sum(0), table[sel_idx, FIELDS:].sum(0)
         per_image_tiles = np.bincount(image[chosen], minlength=M) if chosen else np.zeros(M, dtype=np.int64)
-        report = {"dataset": _source_name(args), "subset": args.subset, "task": args.task, "num_classes": nc,
+        report = {"dataset": rc.source_name(args), "subset": args.subset, "task": args.task, "num_classes": nc,
                   "kind": args.kind, "by": args.by, "tile": list(tile), "size": list(size), "budget": args.budget,
                   "max_per_image": args.max_per_image, "seed": args.seed, "images": M, "total_pixels": total,
                   "pixels_asked": budget_pixels, "pixels_spent": spent, "spent_share": spent / total,
@@ -484,7 +440,7 @@ def main(args):
                 hc.PngWriter(pool, images_dir)
             empty = np.full(size, 255, dtype=np.uint8)
             i0 = 0
-            for s, images, target in _batches(args, nc, pool, dev):
+            for s, images, target in rc.image_or_dataset_batches(args, nc, pool, dev, unique_stems=True):
                 n = len(s)
                 idx = [j for j in range(n) if everywhere or (i0 + j) in set(touched)]
                 for png in (map_png, tree_png, image_png):

@@ -29,7 +29,6 @@ thresholds per class and prefer a held-out split (``--fit`` on one split, ``--th
 And, as with every add-on here, everything was measured on a randomly initialised network only: the
 kernels' arithmetic and speed are tested, the usefulness of the issues on a trained head is not."""
 import os
-from argparse import Namespace
 
 import torch
 
@@ -47,35 +46,17 @@ GIVEN = "given"                                 # q_class: the q of the pixel's 
 GREY = 128
 
 
-def q_values(qmap):
-    """A stored q map as int64 (uint16 tensors support few operations)."""
-    return qmap.view(torch.int16).to(torch.int64) & 0xffff
+q_values = hc.q_values                          # a stored q map as int64
+check_id = hc.check_id
 
 
 def check_nc(fn, nc):
-    nc = int(nc)
-    if not _audit_lib.MIN_CLASSES <= nc <= _audit_lib.MAX_CLASSES:
-        raise RuntimeError(f"mdil {fn}: {nc} classes (supported: {_audit_lib.MIN_CLASSES} to "
-                           f"{_audit_lib.MAX_CLASSES})")
-    return nc
+    return hc.check_nc(fn, _audit_lib, nc)
 
 
 def check_thr(fn, thr, nc):
     """-> the thresholds as a list of nc ints in [0, 65536]."""
-    try:
-        t = [int(v) for v in (thr.tolist() if isinstance(thr, torch.Tensor) else thr)]
-    except (TypeError, ValueError):
-        raise RuntimeError(f"mdil {fn}: thr must be {nc} integers, got {thr!r}") from None
-    if len(t) != nc or any(v < 0 or v > Q_ONE for v in t):
-        raise RuntimeError(f"mdil {fn}: thr must be {nc} integers in [0, {Q_ONE}] (class c is confident when "
-                           f"q_c >= thr[c]), got {t}")
-    return t
-
-
-def check_id(fn, name, v):
-    if not 0 <= int(v) <= 255:
-        raise RuntimeError(f"mdil {fn}: {name} {v} outside [0, 255]")
-    return int(v)
+    return hc.check_q_thresholds(fn, thr, nc, Q_ONE, "class c is confident when q_c >= thr[c]")
 
 
 def head_counter_shapes(nc, N):
@@ -85,8 +66,7 @@ def head_counter_shapes(nc, N):
 
 def new_head_counters(nc, N, dev, names=HEAD_COUNTERS):
     """The int64 counters of ``audit_head`` for ``nc`` classes and a batch of ``N`` images, zeroed, on ``dev``."""
-    shapes = head_counter_shapes(nc, N)
-    return {k: torch.zeros(shapes[k], dtype=torch.int64, device=dev) for k in names}
+    return hc.zero_counters(head_counter_shapes(nc, N), dev, names)
 
 
 def apply_counter_shapes(nc):
@@ -94,21 +74,7 @@ def apply_counter_shapes(nc):
 
 
 def new_apply_counters(nc, dev):
-    return {k: torch.zeros(s, dtype=torch.int64, device=dev) for k, s in apply_counter_shapes(nc).items()}
-
-
-def _device_ints(fn, values, name, nc, dev, lo, hi):
-    """nc ints in [lo, hi] or an int32 [nc] device tensor (taken as it is) -> the device tensor."""
-    if isinstance(values, torch.Tensor) and values.is_cuda:
-        hc.check_tables(fn, _PATH, dev, torch.int32, ((values, name, (nc,)),))
-        return values
-    try:
-        v = [int(t) for t in (values.tolist() if isinstance(values, torch.Tensor) else values)]
-    except (TypeError, ValueError):
-        raise RuntimeError(f"mdil {fn}: {name} must be {nc} integers, got {values!r}") from None
-    if len(v) != nc or any(t < lo or t > hi for t in v):
-        raise RuntimeError(f"mdil {fn}: {name} must be {nc} integers in [{lo}, {hi}], got {v}")
-    return torch.tensor(v, dtype=torch.int32).to(dev)
+    return hc.zero_counters(apply_counter_shapes(nc), dev)
 
 
 # --------------------------------------------------------------------------------- entry points
@@ -152,7 +118,7 @@ def audit_head(features, weight, bias, target=None, ignore_index=-1, thr=None, q
     if q_class is None and not want_suggest and all(v is None for v in c.values()):
         raise RuntimeError(f"mdil {fn}: nothing to do (no qmap, no suggest map, no counters)")
     with torch.no_grad(), torch.cuda.device(dev):
-        thr_d = None if thr is None else _device_ints(fn, thr, "thr", nc, dev, 0, Q_ONE)
+        thr_d = None if thr is None else hc.device_ints(fn, _PATH, thr, "thr", nc, dev, 0, Q_ONE)
         qmap = torch.empty(N, 2 * H, 2 * W, dtype=QMAP, device=dev) if q_class is not None else None
         suggest = torch.empty(N, 2 * H, 2 * W, dtype=torch.uint8, device=dev) if want_suggest else None
         _audit_lib.check(
@@ -194,7 +160,7 @@ def audit_apply(target, suggest, selfq, nc, max_q, mode="prune", ignore_index=-1
     if not want_out and not want_mask and all(v is None for v in c.values()):
         raise RuntimeError(f"mdil {fn}: nothing to do (no out map, no mask, no counters)")
     with torch.no_grad(), torch.cuda.device(dev):
-        max_q_d = _device_ints(fn, max_q, "max_q", nc, dev, -1, Q_ONE - 1)
+        max_q_d = hc.device_ints(fn, _PATH, max_q, "max_q", nc, dev, -1, Q_ONE - 1)
         out = torch.empty_like(target) if want_out else None
         mask = torch.empty_like(target) if want_mask else None
         _audit_lib.check(
@@ -371,29 +337,9 @@ def read_thresholds(path, nc):
     return check_thr("--thresholds", saved["thr"], nc)
 
 
-def _source_name(args):
-    return "synthetic" if args.synthetic else args.dataset
-
-
 def plan_clean_tree(args):
-    """The folders of ``--clean-root`` and the label file of every image, in the order of the batches.
-    A dataset's images are linked (``pseudo.plan_tree``); procedural images have no files, so they are
-    written beside their labels.  -> (labels' folder, label names, images' folder or None)"""
-    from . import pseudo as P
-    img_dir, lab_dir = P.LAYOUTS[args.layout]
-    if args.synthetic:
-        images = os.path.join(args.clean_root, img_dir, args.subset)
-        labels = os.path.join(args.clean_root, lab_dir, args.subset)
-        os.makedirs(images, exist_ok=True)
-        os.makedirs(labels, exist_ok=True)
-        stems = [f"synthetic_{j:04d}" for j in range(args.synthetic)]
-        return labels, [P.label_name(args.layout, s) for s in stems], images
-    from .dataset import open_dataset
-    ds = open_dataset(args.dataset, args.subset, args, augment=False)
-    base = getattr(ds, "base", ds)
-    plan = Namespace(images=base.images_root, layout=args.layout, out_root=args.clean_root, subset=args.subset)
-    labels, names = P.plan_tree(plan, base.filenames)
-    return labels, names, None
+    """The label tree of ``--clean-root`` -> (labels' folder, label names, images' folder or None)."""
+    return rc.plan_label_tree(args, args.clean_root)
 
 
 def main(args):
@@ -406,7 +352,7 @@ def main(args):
     dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
     ignore = nc - 1                                    # the trainers' relabelled ignore class
     meter = LabelAuditor(nc, ignore, 255)
-    report = {"dataset": _source_name(args), "subset": args.subset, "task": args.task, "num_classes": nc,
+    report = {"dataset": rc.source_name(args), "subset": args.subset, "task": args.task, "num_classes": nc,
               "ignore_index": ignore}
     if saved_thr is not None:
         meter.set_thresholds(saved_thr)
@@ -420,7 +366,7 @@ def main(args):
         count, qsum = meter.fitted["count"].tolist(), meter.fitted["qsum"].tolist()
         report.update(fit_images=n, fit_count=count, fit_qsum=qsum)
         if args.fit:
-            hc.write_json({"mode": "fit", "dataset": _source_name(args), "subset": args.subset, "task": args.task,
+            hc.write_json({"mode": "fit", "dataset": rc.source_name(args), "subset": args.subset, "task": args.task,
                            "num_classes": nc, "ignore_index": ignore, "images": n, "thr": thr, "count": count,
                            "qsum": qsum, "nonfinite": int(meter.fitted["nonfinite"].item())}, args.fit)
             print(f"thresholds of {n} images written to {args.fit}")

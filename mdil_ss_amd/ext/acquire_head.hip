@@ -27,9 +27,10 @@
 //      1, after kTileRounds tile rounds the lanes that are left add for themselves: a 2 x 2 tile (every lane
 //      a tile of its own) pays the rounds and then what it would have paid anyway.
 //   2. In the work-group, an add goes to a direct-mapped table of kCacheSlots (cell, 32-bit count) pairs in
-//      LDS, openset_head.hip's: the slot is claimed by a compare-and-swap on its cell index; a slot that
-//      another cell holds sends the add to global memory instead.  The table is flushed to the global table
-//      by 64-bit atomics (relaxed, agent scope) after the work-group's loop and every kFlushEvery trips.
+//      LDS, openset_head.hip's (map_common.h's cached_add and flush_cache): the slot is claimed by a
+//      compare-and-swap on its cell index; a slot that another cell holds sends the add to global memory
+//      instead.  The table is flushed to the global table by 64-bit atomics (relaxed, agent scope) after the
+//      work-group's loop and every kFlushEvery trips.
 // A slot cannot wrap: between two flushes a work-group sees kFlushEvery * 1024 output pixels, and the largest
 // field, the sum of q, grows by at most 65,535 per pixel: 31 * 1024 * 65,535 < 2^32 (static_assert below).
 // Integer sums: the result does not depend on the order of arrival, nor on the grid.
@@ -41,10 +42,9 @@
 // runs of equal keys inside a lane's 8 pixels are one LDS atomic, and a work-group flushes its non-zero
 // counters every kApplyFlushEvery trips and at its end by 64-bit global atomics.
 #include "../../include/mdil_acquire.h"
-#include "head_common.h"
+#include "map_common.h"
 
 #include <float.h>
-#include <math.h>
 
 namespace {
 
@@ -53,61 +53,22 @@ constexpr int kFields = MDIL_ACQUIRE_TILE_FIELDS;
 constexpr int kHeadWG = 256;                         // 4 wavefronts of 64 lanes
 constexpr int kHeadMaxBlocks = 768;                  // three per CU; beyond 196,608 feature pixels the loop strides
 constexpr int kCacheSlots = 4096;                    // LDS table of (cell, count): 32 KB
-constexpr uint32_t kEmptySlot = 0xffffffffu;         // no cell: cells are below 2^31
 constexpr int kTileRounds = 8;                       // ballot rounds over tiles per feature pixel
 constexpr int kLabelRounds = 4;                      // ballot rounds over labels per tile round
 constexpr int kFlushEvery = 31;                      // trips between two flushes of the LDS table
 constexpr int kMapWG = 256;
 constexpr int kMapMaxBlocks = 512;                   // beyond 131,072 items (of 8 pixels) the loop strides
-constexpr int kPerItem = 8;
 constexpr int kApplyFlushEvery = 1 << 19;            // trips; a trip adds at most 2048 counts per work-group
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr char kFnHead[] = "acquire_head";
 constexpr char kFnApply[] = "acquire_apply";
 
 static_assert((long long)kFlushEvery * kHeadWG * 4 * 65535 < (1LL << 32), "a 32-bit LDS slot could wrap");
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ bool is_finite(float v) { return fabsf(v) < INFINITY; }   // false for a NaN
 
 // q = min(65535, (uint32)(max(u, 0) * 65536)): the scaling is exact, the cast truncates.  The comparisons keep a
 // NaN and the negatives out of the cast (a NaN is not >= anything: it is sent to 0).
 __device__ __forceinline__ uint32_t quantise(float u) {
   const float v = u * 65536.0f;
   return v >= 65535.0f ? 65535u : (v >= 0.0f ? (uint32_t)v : 0u);
-}
-
-// Sum over the 64 lanes of a wave, every lane active.  Values below 2^26: the sum fits.
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-  return v;
-}
-
-// tiles[cell] += n by way of the work-group's table: the slot's entry is claimed for its cell or found to hold
-// it already; an entry that holds another cell sends the add to global memory.
-__device__ __forceinline__ void cached_add(u64* __restrict__ tiles, uint32_t* tags, uint32_t* counts, uint32_t cell,
-                                           uint32_t n) {
-  const uint32_t h = (cell * 2654435761u) >> 20;                   // 12 bits: below kCacheSlots
-  const uint32_t old = atomicCAS(&tags[h], kEmptySlot, cell);
-  if (old == kEmptySlot || old == cell)
-    atomicAdd(&counts[h], n);
-  else
-    __hip_atomic_fetch_add(tiles + cell, (u64)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The occupied slots -> the global table, by the whole work-group; the caller's barriers surround it.
-__device__ __forceinline__ void flush_cache(u64* __restrict__ tiles, uint32_t* tags, uint32_t* counts) {
-  for (int i = threadIdx.x; i < kCacheSlots; i += kHeadWG) {
-    const uint32_t cell = tags[i];
-    if (cell != kEmptySlot) {
-      const uint32_t v = counts[i];
-      if (v) __hip_atomic_fetch_add(tiles + cell, (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      tags[i] = kEmptySlot;
-      counts[i] = 0u;
-    }
-  }
 }
 
 // What one lane holds after its four parities.  packed: pixels | wrong << 10 | valid << 20 (each at most 4, a
@@ -132,11 +93,11 @@ __device__ __forceinline__ void wave_merged_adds(u64* __restrict__ tiles, uint32
     const uint32_t pk = wave_sum_u32(match ? L.packed : 0u);
     const uint32_t qs = wave_sum_u32(match ? L.qs : 0u);
     if (lane == leader) {
-      cached_add(tiles, tags, counts, c0, pk & 1023u);
-      if (qs) cached_add(tiles, tags, counts, c0 + 1u, qs);
+      cached_add<kCacheSlots>(tiles, tags, counts, c0, pk & 1023u);
+      if (qs) cached_add<kCacheSlots>(tiles, tags, counts, c0 + 1u, qs);
       if (with_target) {
-        if ((pk >> 10) & 1023u) cached_add(tiles, tags, counts, c0 + 2u, (pk >> 10) & 1023u);
-        if (pk >> 20) cached_add(tiles, tags, counts, c0 + 3u, pk >> 20);
+        if ((pk >> 10) & 1023u) cached_add<kCacheSlots>(tiles, tags, counts, c0 + 2u, (pk >> 10) & 1023u);
+        if (pk >> 20) cached_add<kCacheSlots>(tiles, tags, counts, c0 + 3u, pk >> 20);
       }
     }
     // the labels of the matched lanes
@@ -153,25 +114,27 @@ __device__ __forceinline__ void wave_merged_adds(u64* __restrict__ tiles, uint32
         n += (uint32_t)__popcll(__ballot(hit));
         left = hit ? left & ~(1u << j) : left;
       }
-      if (lane == first) cached_add(tiles, tags, counts, c0 + (uint32_t)kFields + l0, n);
+      if (lane == first) cached_add<kCacheSlots>(tiles, tags, counts, c0 + (uint32_t)kFields + l0, n);
       open = __ballot(left != 0u);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (left >> j & 1u) cached_add(tiles, tags, counts, c0 + (uint32_t)kFields + label_of(L.labels, j), 1u);
+      if (left >> j & 1u)
+        cached_add<kCacheSlots>(tiles, tags, counts, c0 + (uint32_t)kFields + label_of(L.labels, j), 1u);
     active = active && !match;
     todo &= ~same;
   }
   if (active) {                                                    // a lane of a tile no round reached
-    cached_add(tiles, tags, counts, L.cell0, L.packed & 1023u);
-    if (L.qs) cached_add(tiles, tags, counts, L.cell0 + 1u, L.qs);
+    cached_add<kCacheSlots>(tiles, tags, counts, L.cell0, L.packed & 1023u);
+    if (L.qs) cached_add<kCacheSlots>(tiles, tags, counts, L.cell0 + 1u, L.qs);
     if (with_target) {
-      if ((L.packed >> 10) & 1023u) cached_add(tiles, tags, counts, L.cell0 + 2u, (L.packed >> 10) & 1023u);
-      if (L.packed >> 20) cached_add(tiles, tags, counts, L.cell0 + 3u, L.packed >> 20);
+      if ((L.packed >> 10) & 1023u) cached_add<kCacheSlots>(tiles, tags, counts, L.cell0 + 2u, (L.packed >> 10) & 1023u);
+      if (L.packed >> 20) cached_add<kCacheSlots>(tiles, tags, counts, L.cell0 + 3u, L.packed >> 20);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (L.left >> j & 1u) cached_add(tiles, tags, counts, L.cell0 + (uint32_t)kFields + label_of(L.labels, j), 1u);
+      if (L.left >> j & 1u)
+        cached_add<kCacheSlots>(tiles, tags, counts, L.cell0 + (uint32_t)kFields + label_of(L.labels, j), 1u);
   }
 }
 
@@ -218,10 +181,7 @@ __global__ __launch_bounds__(kHeadWG, 2) void acquire_head_kernel(
     const int h = (int)(r - n * H), col = (int)(p - r * W);
     const long long o0 = (2 * r * 2 * W) + 2 * col;                // pixel (2h, 2w); row below: + 2W
     uint32_t given = 0u;                                           // byte a*2+b
-    if (target) {
-      given = (uint32_t) * reinterpret_cast<const uint16_t*>(target + o0) |
-              (uint32_t) * reinterpret_cast<const uint16_t*>(target + o0 + 2LL * W) << 16;
-    }
+    if (target) given = quad_bytes(target, o0, W);
     Lane L;
     L.cell0 = (uint32_t)((n * Ty + (2 * h) / th) * Tx + (2 * col) / tw) * row;   // below 2^31 (checked by the host)
     L.packed = L.qs = L.labels = L.left = 0u;
@@ -230,7 +190,10 @@ __global__ __launch_bounds__(kHeadWG, 2) void acquire_head_kernel(
 #pragma unroll 1
     for (int par = 0; par < 4; ++par) {
       float d[kMaxC];
-      // the logits of this parity: bias first, then ci ascending (predict_head.hip's chain)
+      // The logits of this parity: bias first, then ci ascending.  map_common.h's stage_parity and parity_logits,
+      // spelled out here and above: through the helpers the compiler schedules this kernel differently (same
+      // registers, same length) and the variants with tiles ran 1 to 1.5 % slower than before, past the
+      // run-to-run margin (profiles/map_common_ab.json); spelled out, the kernel's code is what it was.
 #pragma unroll
       for (int c = 0; c < kMaxC; ++c) {
         if (c < nc) {
@@ -305,7 +268,7 @@ __global__ __launch_bounds__(kHeadWG, 2) void acquire_head_kernel(
       if (++trips == kFlushEvery) {                                // uniform over the work-group
         trips = 0;
         __syncthreads();
-        flush_cache(tiles, tags, counts);
+        flush_cache<kHeadWG, kCacheSlots>(tiles, tags, counts);
         __syncthreads();
       }
     }
@@ -318,68 +281,7 @@ __global__ __launch_bounds__(kHeadWG, 2) void acquire_head_kernel(
     if (nonfinite && nf) __hip_atomic_fetch_add(nonfinite, (u64)nf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (bad_targets && bt) __hip_atomic_fetch_add(bad_targets, (u64)bt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (tiles) flush_cache(tiles, tags, counts);
-}
-
-// A run of equal keys: `add(key)` extends it or, on another key, sends it to counters[key] as one
-// LDS atomic; `done()` sends the last run.
-struct Run {
-  uint32_t* counters;
-  int key;
-  uint32_t n;
-  __device__ __forceinline__ explicit Run(uint32_t* c) : counters(c), key(-1), n(0u) {}
-  __device__ __forceinline__ void done() {
-    if (key >= 0) atomicAdd(&counters[key], n);
-    key = -1;
-    n = 0u;
-  }
-  __device__ __forceinline__ void add(int k) {
-    if (k != key) {
-      done();
-      key = k;
-    }
-    ++n;
-  }
-};
-
-// Eight bytes of a u8 map at item offset o: one packed load where the item is whole, bytes otherwise.
-__device__ __forceinline__ void load_bytes(const unsigned char* __restrict__ map, long long o, int n,
-                                           uint32_t (&v)[kPerItem]) {
-  if (n == kPerItem) {
-    const uint2 t = *reinterpret_cast<const uint2*>(map + o);
-    const uint32_t tw[2] = {t.x, t.y};
-#pragma unroll
-    for (int j = 0; j < kPerItem; ++j) v[j] = (tw[j >> 2] >> (8 * (j & 3))) & 0xffu;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kPerItem; ++j) v[j] = j < n ? (uint32_t)map[o + j] : 0u;
-  }
-}
-
-__device__ __forceinline__ void store_bytes(unsigned char* __restrict__ map, long long o, int n,
-                                            const uint32_t (&v)[kPerItem]) {
-  if (n == kPerItem) {
-    uint2 t;
-    t.x = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
-    t.y = v[4] | v[5] << 8 | v[6] << 16 | v[7] << 24;
-    *reinterpret_cast<uint2*>(map + o) = t;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kPerItem; ++j)
-      if (j < n) map[o + j] = (unsigned char)v[j];
-  }
-}
-
-// counters[i] (32-bit, LDS) -> global[i] (64-bit), the non-zero ones, by the whole work-group; a
-// NULL destination only clears them.  The caller's barriers surround it.
-__device__ __forceinline__ void flush_counters(uint32_t* counters, int n, u64* global) {
-  for (int i = threadIdx.x; i < n; i += kMapWG) {
-    const uint32_t v = counters[i];
-    if (v) {
-      if (global) __hip_atomic_fetch_add(global + i, (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      counters[i] = 0u;
-    }
-  }
+  if (tiles) flush_cache<kHeadWG, kCacheSlots>(tiles, tags, counts);
 }
 
 __global__ __launch_bounds__(kMapWG) void acquire_apply_kernel(
@@ -480,9 +382,9 @@ __global__ __launch_bounds__(kMapWG) void acquire_apply_kernel(
     if (last || ++trips == kApplyFlushEvery) {                     // uniform over the work-group
       trips = 0;
       __syncthreads();
-      flush_counters(Al, nc, annotated);
-      flush_counters(Kl, nc, kept);
-      flush_counters(Fl, nc, filled);
+      flush_counters<kMapWG>(Al, nc, annotated);
+      flush_counters<kMapWG>(Kl, nc, kept);
+      flush_counters<kMapWG>(Fl, nc, filled);
       if (threadIdx.x == 0) {
         if (shown_l && shown) __hip_atomic_fetch_add(shown, (u64)shown_l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (bad_t && bad_targets) __hip_atomic_fetch_add(bad_targets, (u64)bad_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -37,15 +37,15 @@
 // loop (static_assert below).  qsum grows by up to 65,535 per pixel: its LDS counters are 64-bit.  Integer
 // sums: the result does not depend on the order of arrival.
 //
-// audit_apply.  pseudo_apply's layout: a lane owns 8 consecutive pixels (8-byte target and suggest loads, one
-// 16-byte selfq load, 8-byte out and mask stores; the last item of an odd-sized map goes byte by byte); the
-// counters live in LDS as 32-bit integers, runs of equal keys inside a lane's 8 pixels are one LDS atomic, and
-// a work-group flushes its non-zero counters every kFlushEvery trips and at its end by 64-bit global atomics.
+// audit_apply.  pseudo_apply's layout (map_common.h's Run, load_bytes, store_bytes and flush_counters): a lane
+// owns 8 consecutive pixels (8-byte target and suggest loads, one 16-byte selfq load, 8-byte out and mask
+// stores; the last item of an odd-sized map goes byte by byte); the counters live in LDS as 32-bit integers,
+// runs of equal keys inside a lane's 8 pixels are one LDS atomic, and a work-group flushes its non-zero
+// counters every kFlushEvery trips and at its end by 64-bit global atomics.
 #include "../../include/mdil_audit.h"
-#include "head_common.h"
+#include "map_common.h"
 
 #include <float.h>
-#include <math.h>
 
 namespace {
 
@@ -56,28 +56,15 @@ constexpr int kMergeRounds = 4;                      // ballot rounds per parity
                                                      // compiler unrolls them: 186 VGPRs, two waves per SIMD, 1.5 x the time
 constexpr int kMapWG = 256;
 constexpr int kMapMaxBlocks = 512;                   // beyond 131,072 items (of 8 pixels) the loop strides
-constexpr int kPerItem = 8;
 constexpr int kFlushEvery = 1 << 19;                 // trips; a trip adds at most 2048 counts per work-group
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr char kFnHead[] = "audit_head";
 constexpr char kFnApply[] = "audit_apply";
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ bool is_finite(float v) { return fabsf(v) < INFINITY; }   // false for a NaN
 
 // The quantisation rule of pseudo_head.hip: p * 65536 is exact, the cast truncates, p = 1 gives 65535.
 // The comparison first keeps a NaN out of the cast (a NaN is not >= anything: it is sent to 0).
 __device__ __forceinline__ uint32_t quantise(float p) {
   const float v = p * 65536.0f;
   return v >= 65535.0f ? 65535u : (v >= 0.0f ? (uint32_t)v : 0u);
-}
-
-// Sum over the 64 lanes of a wave, every lane active.  Values below 2^26: the sum fits.
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);
-  return v;
 }
 
 // The work-group's tables and where they go.
@@ -135,19 +122,6 @@ __device__ __forceinline__ void wave_merged_adds(const Tables& T, bool active, u
     todo &= ~same;
   }
   if (active) add_group(T, t, n, 1u, qt, sug == t ? 1u : 0u, sug == nc ? 1u : 0u, sug != t && sug != nc ? 1u : 0u);
-}
-
-// counters[i] (32-bit, LDS) -> global[i] (64-bit), the non-zero ones, by the whole work-group; a
-// NULL destination only clears them.  The caller's barriers surround it.
-template <int WG>
-__device__ __forceinline__ void flush_counters(uint32_t* counters, int n, u64* global) {
-  for (int i = threadIdx.x; i < n; i += WG) {
-    const uint32_t v = counters[i];
-    if (v) {
-      if (global) __hip_atomic_fetch_add(global + i, (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      counters[i] = 0u;
-    }
-  }
 }
 
 // Occupancy: __launch_bounds__(256, 2) as openset_head, with the 32 logits of a parity and the 16 features in
@@ -223,16 +197,16 @@ __global__ __launch_bounds__(kHeadWG, 2) void audit_head_kernel(
     const int n = (int)(p / HW);
     const long long o0 = (2 * r * 2 * W) + 2 * (p - r * W);        // pixel (2h, 2w); row below: + 2W
     uint32_t given = 0u;                                           // byte a*2+b
-    if (target) {
-      given = (uint32_t) * reinterpret_cast<const uint16_t*>(target + o0) |
-              (uint32_t) * reinterpret_cast<const uint16_t*>(target + o0 + 2LL * W) << 16;
-    }
+    if (target) given = quad_bytes(target, o0, W);
     uint32_t sugs = 0u, q_top = 0u, q_bottom = 0u;                 // byte a*2+b; the two pixels of a row
 
 #pragma unroll 1
     for (int par = 0; par < 4; ++par) {
       float d[kMaxC];
-      // the logits of this parity: bias first, then ci ascending (predict_head.hip's chain)
+      // The logits of this parity: bias first, then ci ascending.  map_common.h's stage_parity and parity_logits,
+      // spelled out here and above: through the helpers the compiler schedules this kernel differently (same
+      // registers, same occupancy) and sweep 2 ran 0.5 to 0.9 % slower than before, past the run-to-run margin
+      // (profiles/map_common_ab.json); spelled out, the kernel's code is what it was.
 #pragma unroll
       for (int c = 0; c < kMaxC; ++c) {
         if (c < nc) {
@@ -328,55 +302,6 @@ __global__ __launch_bounds__(kHeadWG, 2) void audit_head_kernel(
   if (qsum) {
     for (int i = threadIdx.x; i < nc; i += kHeadWG)
       if (Ql[i]) __hip_atomic_fetch_add(qsum + i, Ql[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// A run of equal keys: `add(key)` extends it or, on another key, sends it to counters[key] as one
-// LDS atomic; `done()` sends the last run.
-struct Run {
-  uint32_t* counters;
-  int key;
-  uint32_t n;
-  __device__ __forceinline__ explicit Run(uint32_t* c) : counters(c), key(-1), n(0u) {}
-  __device__ __forceinline__ void done() {
-    if (key >= 0) atomicAdd(&counters[key], n);
-    key = -1;
-    n = 0u;
-  }
-  __device__ __forceinline__ void add(int k) {
-    if (k != key) {
-      done();
-      key = k;
-    }
-    ++n;
-  }
-};
-
-// Eight bytes of a u8 map at item offset o: one packed load where the item is whole, bytes otherwise.
-__device__ __forceinline__ void load_bytes(const unsigned char* __restrict__ map, long long o, int n,
-                                           uint32_t (&v)[kPerItem]) {
-  if (n == kPerItem) {
-    const uint2 t = *reinterpret_cast<const uint2*>(map + o);
-    const uint32_t tw[2] = {t.x, t.y};
-#pragma unroll
-    for (int j = 0; j < kPerItem; ++j) v[j] = (tw[j >> 2] >> (8 * (j & 3))) & 0xffu;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kPerItem; ++j) v[j] = j < n ? (uint32_t)map[o + j] : 0u;
-  }
-}
-
-__device__ __forceinline__ void store_bytes(unsigned char* __restrict__ map, long long o, int n,
-                                            const uint32_t (&v)[kPerItem]) {
-  if (n == kPerItem) {
-    uint2 t;
-    t.x = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
-    t.y = v[4] | v[5] << 8 | v[6] << 16 | v[7] << 24;
-    *reinterpret_cast<uint2*>(map + o) = t;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kPerItem; ++j)
-      if (j < n) map[o + j] = (unsigned char)v[j];
   }
 }
 

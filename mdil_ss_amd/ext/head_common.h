@@ -1,9 +1,9 @@
-// What the five head add-ons share, written once.  Private to mdil_ss_amd/ext (not under include/):
-// it is compiled INTO each of the five libraries, which stay self-contained binaries -- the error
+// What the eleven head add-ons share, written once.  Private to mdil_ss_amd/ext (not under include/):
+// it is compiled INTO each of the eleven libraries, which stay self-contained binaries -- the error
 // buffer below is one per library -- and it shares nothing with csrc/, similarity.hip or tsne.hip.
 // The arithmetic contracts (order of operations, roundings) are documented in the kernels' header
 // comments; the helpers here are the single spelling of the steps they name.  Who uses what:
-//   every head      set_error, bounded_grid, launched, classes_ok
+//   every head      set_error, bounded_grid, launched, classes_ok (boundary, segments, signif: these alone)
 //   predict         vote, stage_head, logits4, colour_ok
 //   fullres         axis, gather, stage_head, confusion_zero, out_size_ok, colour_ok, scoring_ok
 //   ensemble        vote, axis, gather, confusion_zero, out_size_ok, colour_ok, scoring_ok
@@ -11,8 +11,12 @@
 //   calib           vote, fold_kernel (and through it wave_sum), shape_ok, ignore_ok, workspace_ok
 //   route           vote, wave_sum, shape_ok, workspace_ok (its own per-image fold; calib_head's chain and forms at T = 1)
 //   refine          vote, stage_head, scoring_ok (logits4's chain for the one parity a lane owns)
-//   audit           vote, shape_ok, ignore_ok (openset_head's Wp staging and chain; its own helpers live in audit_head.hip)
-//   acquire         vote, shape_ok, ignore_ok (route_head's Wp staging and chain; its own helpers live in acquire_head.hip)
+//   pseudo          vote, stage_head, logits4, ignore_ok
+//   openset         vote
+//   audit           vote, shape_ok, ignore_ok
+//   acquire         vote, shape_ok, ignore_ok
+// pseudo, openset, audit, acquire and route share more through map_common.h, which includes this header: the
+// per-parity Wp staging and chain, the LDS tables of integer adds and the helpers of the map kernels.
 // calib_head.hip forms its logits per parity from its own Wp[a*2+b][c][ci] staging, not through
 // logits4 (another LDS layout, the same chain), and keeps its DPP sums.
 #pragma once

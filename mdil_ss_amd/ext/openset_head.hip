@@ -6,8 +6,8 @@
 //                  are never stored.
 //   openset_apply  stored maps -> the label map with a reject id, the 8-bit score map, their counters
 //
-// The chain is route_head.hip's, spelled the same way (Wp[a*2+b][c][ci] in LDS, the logits of one parity in
-// registers, vote, then c ascending: d_c, one hardware exp2, s, A), so `label` is predict_head's bits and
+// The chain is route_head.hip's, through the same helpers of map_common.h (Wp[a*2+b][c][ci] in LDS, the logits of
+// one parity in registers, vote, then c ascending: d_c, one hardware exp2, s, A), so `label` is predict_head's bits and
 // `ent` route_head's.  From m, s, A:  conf = 1 / s,  logs = logf(s),  ent = logs - A conf, and
 //      msp = (s - 1) conf,  maxlogit = -m,  energy = -(m + logs),  entropy = ent,      each + 0.0f.
 // The code of a score is the high half of the usual radix-sort key of its bits (sign flipped for positive
@@ -25,12 +25,13 @@
 //      carries their number as ONE add, and the matched lanes retire.  After kMergeRounds rounds whatever is
 //      left goes on as adds of 1: an image region of one texture merges in a round or two, white noise pays
 //      kMergeRounds ballots and then what it would have paid anyway.
-//   2. In the work-group, an add goes to a direct-mapped table of kCacheSlots (key, 32-bit count) pairs in
-//      LDS: the slot is claimed by a compare-and-swap on its key; a slot that another key holds sends the
-//      add to global memory instead.  After its loop the work-group adds its occupied slots to the global
-//      table.  The grid is at most kHeadMaxBlocks work-groups, so a code that every pixel shares costs that
-//      many global atomics, not one per wave and parity (measured first without this stage: 0.6 ms on
-//      all-zero features, 2.7 ms on the network's, against 0.08 ms for the kernel without a histogram).
+//   2. In the work-group, an add goes to a direct-mapped table of kCacheSlots (key, 32-bit count) pairs in LDS
+//      (map_common.h's cached_add and flush_cache): the slot is claimed by a compare-and-swap on its key; a
+//      slot that another key holds sends the add to global memory instead.  After its loop the work-group adds
+//      its occupied slots to the global table.  The grid is at most kHeadMaxBlocks work-groups, so a code that
+//      every pixel shares costs that many global atomics, not one per wave and parity (measured first without
+//      this stage: 0.6 ms on all-zero features, 2.7 ms on the network's, against 0.08 ms for the kernel without
+//      a histogram).
 // A slot's count cannot wrap: a work-group sees at most 2^40 / 4 / kHeadMaxBlocks feature pixels of a full
 // grid, four adds of one kind each: under 2^31.  Integer sums: the result does not depend on the order of arrival.
 //
@@ -39,10 +40,9 @@
 // by byte); the counters live in LDS as 32-bit integers, runs of equal keys inside a lane's 8 pixels are one
 // LDS atomic, and a work-group flushes its non-zero counters once by 64-bit global atomics.
 #include "../../include/mdil_openset.h"
-#include "head_common.h"
+#include "map_common.h"
 
 #include <float.h>
-#include <math.h>
 
 namespace {
 
@@ -52,37 +52,18 @@ constexpr int kCodes = MDIL_OPENSET_CODES;
 constexpr int kHeadWG = 256;                         // 4 wavefronts of 64 lanes
 constexpr int kHeadMaxBlocks = 768;                  // three per CU (LDS, registers); beyond 196,608 feature pixels the loop strides
 constexpr int kCacheSlots = 4096;                    // LDS table of (key, count): 32 KB
-constexpr uint32_t kEmptySlot = 0xffffffffu;         // no key: keys are below 8 x 65536
 constexpr int kMergeRounds = 8;                      // ballot rounds per (parity, kind) before plain atomics
 constexpr int kMapWG = 256;
 constexpr int kMapMaxBlocks = 512;                   // beyond 131,072 items (of 8 pixels) the loop strides
-constexpr int kPerItem = 8;
 constexpr int kFlushEvery = 1 << 19;                 // trips; a trip adds at most 2048 counts per work-group
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr char kFnHead[] = "openset_head";
 constexpr char kFnApply[] = "openset_apply";
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ bool is_finite(float v) { return fabsf(v) < INFINITY; }   // false for a NaN
 
 // The 16-bit code of a score: order-preserving over all floats (NaNs aside, which never get here).
 __device__ __forceinline__ uint32_t code16(float u) {
   const uint32_t bits = __float_as_uint(u);
   const uint32_t key = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
   return key >> 16;
-}
-
-// hist[slot] += n by way of the work-group's table: the slot's entry is claimed for its key or found to hold
-// it already; an entry that holds another key sends the add to global memory.
-__device__ __forceinline__ void cached_add(u64* __restrict__ hist, uint32_t* tags, uint32_t* counts, uint32_t slot,
-                                           uint32_t n) {
-  const uint32_t h = (slot * 2654435761u) >> 20;                   // 12 bits: below kCacheSlots
-  const uint32_t old = atomicCAS(&tags[h], kEmptySlot, slot);
-  if (old == kEmptySlot || old == slot)
-    atomicAdd(&counts[h], n);
-  else
-    __hip_atomic_fetch_add(hist + slot, (u64)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // One add per distinct `slot` among the lanes of the wave with `active`: every lane of the wave calls it
@@ -95,11 +76,11 @@ __device__ __forceinline__ void wave_merged_add(u64* __restrict__ hist, uint32_t
     const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
     const uint32_t s0 = (uint32_t)__builtin_amdgcn_readlane((int)slot, leader);
     const u64 same = __ballot(active && slot == s0);
-    if (lane == leader) cached_add(hist, tags, counts, s0, (uint32_t)__popcll(same));
+    if (lane == leader) cached_add<kCacheSlots>(hist, tags, counts, s0, (uint32_t)__popcll(same));
     active = active && slot != s0;
     todo &= ~same;
   }
-  if (active) cached_add(hist, tags, counts, slot, 1u);
+  if (active) cached_add<kCacheSlots>(hist, tags, counts, slot, 1u);
 }
 
 // 2 waves per SIMD like route_head: the 32 logits of a parity stay in registers
@@ -113,19 +94,14 @@ __global__ __launch_bounds__(kHeadWG, 2) void openset_head_kernel(
   __shared__ uint32_t Gl[256];                                       // group of a target byte
   __shared__ uint32_t Tl[kCacheSlots], Cl[kCacheSlots];              // the histogram's table: key, count
   __shared__ uint32_t nf;
-  static_assert(kCacheSlots == 1 << 12, "cached_add keeps 12 bits of the hash");
   static_assert(MDIL_OPENSET_MAX_PIXELS / 4 / kHeadMaxBlocks * 4 <= 0x80000000LL, "a slot's count could wrap");
-  for (int i = threadIdx.x; i < nc * 64; i += kHeadWG) {
-    const int k = i & 3, ci = (i >> 2) & 15, c = i >> 6;
-    Wp[k][c][ci] = w[(ci * nc + c) * 4 + k];
-  }
+  stage_parity<kHeadWG>(w, bias, nc, Wp, Bl);
   if (hist) {
     for (int i = threadIdx.x; i < kCacheSlots; i += kHeadWG) {
       Tl[i] = kEmptySlot;
       Cl[i] = 0u;
     }
   }
-  for (int i = threadIdx.x; i < nc; i += kHeadWG) Bl[i] = bias[i];
   for (int i = threadIdx.x; i < 256; i += kHeadWG) Gl[i] = target ? (uint32_t)group_lut[i] : (uint32_t)const_group;
   if (threadIdx.x == 0) nf = 0u;
   __syncthreads();
@@ -141,29 +117,13 @@ __global__ __launch_bounds__(kHeadWG, 2) void openset_head_kernel(
     const long long r = p / W;                                     // n * H + h
     const long long o0 = (2 * r * 2 * W) + 2 * (p - r * W);        // pixel (2h, 2w); row below: + 2W
     uint32_t groups = 0u;                                          // byte a*2+b
-    if (target) {
-      groups = (uint32_t) * reinterpret_cast<const uint16_t*>(target + o0) |
-               (uint32_t) * reinterpret_cast<const uint16_t*>(target + o0 + 2LL * W) << 16;
-    }
+    if (target) groups = quad_bytes(target, o0, W);
     uint32_t labels = 0u, codes_top = 0u, codes_bottom = 0u;       // byte a*2+b; the two pixels of a row
 
 #pragma unroll 1
     for (int par = 0; par < 4; ++par) {
       float d[kMaxC];
-      // the logits of this parity: bias first, then ci ascending (predict_head.hip's chain)
-#pragma unroll
-      for (int c = 0; c < kMaxC; ++c) {
-        if (c < nc) {
-          float a = Bl[c];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const f32x4 wv = *reinterpret_cast<const f32x4*>(&Wp[par][c][k * 4]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a = __builtin_fmaf(xv[k][e], wv[e], a);
-          }
-          d[c] = a;
-        }
-      }
+      parity_logits<kMaxC>(xv, Wp, Bl, par, nc, d);                  // predict_head.hip's chain, per parity
       float m = 0.f;
       int bi = 0;
 #pragma unroll
@@ -230,73 +190,7 @@ __global__ __launch_bounds__(kHeadWG, 2) void openset_head_kernel(
   if (bad) atomicAdd(&nf, bad);
   __syncthreads();                                                 // every lane of the work-group is here
   if (nonfinite && threadIdx.x == 0 && nf) atomicAdd(nonfinite, (u64)nf);
-  if (hist) {
-    for (int i = threadIdx.x; i < kCacheSlots; i += kHeadWG)
-      if (Tl[i] != kEmptySlot && Cl[i])
-        __hip_atomic_fetch_add(hist + Tl[i], (u64)Cl[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// counters[i] (32-bit, LDS) -> global[i] (64-bit), the non-zero ones, by the whole work-group; a
-// NULL destination only clears them.  The caller's barriers surround it.
-template <int WG>
-__device__ __forceinline__ void flush_counters(uint32_t* counters, int n, u64* global) {
-  for (int i = threadIdx.x; i < n; i += WG) {
-    const uint32_t v = counters[i];
-    if (v) {
-      if (global) atomicAdd(global + i, (u64)v);
-      counters[i] = 0u;
-    }
-  }
-}
-
-// A run of equal keys: `add(key)` extends it or, on another key, sends it to counters[key] as one
-// LDS atomic; `done()` sends the last run.
-struct Run {
-  uint32_t* counters;
-  int key;
-  uint32_t n;
-  __device__ __forceinline__ explicit Run(uint32_t* c) : counters(c), key(-1), n(0u) {}
-  __device__ __forceinline__ void done() {
-    if (key >= 0) atomicAdd(&counters[key], n);
-    key = -1;
-    n = 0u;
-  }
-  __device__ __forceinline__ void add(int k) {
-    if (k != key) {
-      done();
-      key = k;
-    }
-    ++n;
-  }
-};
-
-// Eight bytes of a u8 map at item offset o: one packed load where the item is whole, bytes otherwise.
-__device__ __forceinline__ void load_bytes(const unsigned char* __restrict__ map, long long o, int n,
-                                           uint32_t (&v)[kPerItem]) {
-  if (n == kPerItem) {
-    const uint2 t = *reinterpret_cast<const uint2*>(map + o);
-    const uint32_t tw[2] = {t.x, t.y};
-#pragma unroll
-    for (int j = 0; j < kPerItem; ++j) v[j] = (tw[j >> 2] >> (8 * (j & 3))) & 0xffu;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kPerItem; ++j) v[j] = j < n ? (uint32_t)map[o + j] : 0u;
-  }
-}
-
-__device__ __forceinline__ void store_bytes(unsigned char* __restrict__ map, long long o, int n,
-                                            const uint32_t (&v)[kPerItem]) {
-  if (n == kPerItem) {
-    uint2 t;
-    t.x = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;
-    t.y = v[4] | v[5] << 8 | v[6] << 16 | v[7] << 24;
-    *reinterpret_cast<uint2*>(map + o) = t;
-  } else {
-#pragma unroll
-    for (int j = 0; j < kPerItem; ++j)
-      if (j < n) map[o + j] = (unsigned char)v[j];
-  }
+  if (hist) flush_cache<kHeadWG, kCacheSlots>(hist, Tl, Cl);
 }
 
 __global__ __launch_bounds__(kMapWG) void openset_apply_kernel(

@@ -41,7 +41,7 @@
 // are added as one atomic: label maps are piecewise constant, so seen / kept / confusion mostly
 // take one atomic per lane instead of eight on the same address.
 #include "../../include/mdil_pseudo.h"
-#include "head_common.h"
+#include "map_common.h"
 
 namespace {
 
@@ -50,13 +50,10 @@ constexpr int kHeadWG = 1024;                        // 16 wavefronts: one work-
 constexpr int kHeadMaxBlocks = 256;                  // beyond 262,144 feature pixels the loop strides
 constexpr int kMapWG = 256;                          // refine / apply: 4 wavefronts
 constexpr int kMapMaxBlocks = 512;                   // beyond 131,072 items (of 8 pixels) the loop strides
-constexpr int kPerItem = 8;
 constexpr int kFlushEvery = 1 << 19;                 // trips; a trip adds at most 4096 counts per work-group
 constexpr char kFnHead[] = "pseudo_head";
 constexpr char kFnRefine[] = "pseudo_refine";
 constexpr char kFnApply[] = "pseudo_apply";
-
-typedef unsigned long long u64;
 
 // The quantisation rule.  conf * 65536 is exact; the comparison keeps a NaN out of the cast.
 __device__ __forceinline__ uint32_t quantise(float conf, uint32_t& nan_count) {
@@ -67,40 +64,6 @@ __device__ __forceinline__ uint32_t quantise(float conf, uint32_t& nan_count) {
   const float v = conf * 65536.0f;
   return v >= 65535.0f ? 65535u : (uint32_t)v;
 }
-
-// counters[i] (32-bit, LDS) -> global[i] (64-bit), the non-zero ones, by the whole work-group; a
-// NULL destination only clears them.  The caller's barriers surround it.
-template <int WG>
-__device__ __forceinline__ void flush_counters(uint32_t* counters, int n, u64* global) {
-  for (int i = threadIdx.x; i < n; i += WG) {
-    const uint32_t v = counters[i];
-    if (v) {
-      if (global) atomicAdd(global + i, (u64)v);
-      counters[i] = 0u;
-    }
-  }
-}
-
-// A run of equal keys: `add(key)` extends it or, on another key, sends it to counters[key] as one
-// LDS atomic; `done()` sends the last run.  key < 0: nothing to count.
-struct Run {
-  uint32_t* counters;
-  int key;
-  uint32_t n;
-  __device__ __forceinline__ explicit Run(uint32_t* c) : counters(c), key(-1), n(0u) {}
-  __device__ __forceinline__ void done() {
-    if (key >= 0) atomicAdd(&counters[key], n);
-    key = -1;
-    n = 0u;
-  }
-  __device__ __forceinline__ void add(int k) {
-    if (k != key) {
-      done();
-      key = k;
-    }
-    ++n;
-  }
-};
 
 __global__ __launch_bounds__(kHeadWG) void pseudo_head_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,

@@ -35,10 +35,9 @@
 // taps are skipped, not multiplied by zero.  A position's 27 loads are issued together, from clamped
 // addresses, before the first FMA: 162 VGPRs, three waves per SIMD, no scratch.
 #include "../../include/mdil_route.h"
-#include "head_common.h"
+#include "map_common.h"
 
 #include <float.h>
-#include <math.h>
 
 namespace {
 
@@ -49,7 +48,6 @@ constexpr int kMaxBlocksPerImage = 256;              // beyond 65,536 positions 
 constexpr long long kMaxPixels = 1LL << 38;          // positions of a call
 constexpr int kStemOut = MDIL_ROUTE_STEM_CHANNELS, kStemConv = 13, kTaps = 27;
 constexpr int kStemCols = 2 * kStemOut, kHeadCols = 3;
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr char kStemFn[] = "route_stem", kHeadFn[] = "route_head";
 
 // The second launch of both entry points: out[n * cols + c] = the sum of column c over image n's
@@ -81,8 +79,6 @@ __device__ __forceinline__ void store_row(const double (&v)[COLS], double (*part
     row[threadIdx.x] = t;
   }
 }
-
-__device__ __forceinline__ bool is_finite(float v) { return fabsf(v) < INFINITY; }   // false for a NaN
 
 __global__ __launch_bounds__(kWG, 3) void route_stem_kernel(const float* __restrict__ image, const float* __restrict__ w,
                                                          const float* __restrict__ bias, int Hi, int Wi, int bpi,
@@ -199,11 +195,7 @@ __global__ __launch_bounds__(kWG, 2) void route_head_kernel(const float* __restr
   __shared__ float Bl[kMaxC];
   __shared__ double part[kWaves][kHeadCols];
   __shared__ uint32_t nf;
-  for (int i = threadIdx.x; i < nc * 64; i += kWG) {
-    const int k = i & 3, ci = (i >> 2) & 15, c = i >> 6;
-    Wp[k][c][ci] = w[(ci * nc + c) * 4 + k];
-  }
-  for (int i = threadIdx.x; i < nc; i += kWG) Bl[i] = bias[i];
+  stage_parity<kWG>(w, bias, nc, Wp, Bl);
   if (threadIdx.x == 0) nf = 0u;
   __syncthreads();
 
@@ -227,20 +219,7 @@ __global__ __launch_bounds__(kWG, 2) void route_head_kernel(const float* __restr
 #pragma unroll 1
     for (int par = 0; par < 4; ++par) {
       float d[kMaxC];
-      // the logits of this parity: bias first, then ci ascending (predict_head.hip's chain)
-#pragma unroll
-      for (int c = 0; c < kMaxC; ++c) {
-        if (c < nc) {
-          float a = Bl[c];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const f32x4 wv = *reinterpret_cast<const f32x4*>(&Wp[par][c][k * 4]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a = __builtin_fmaf(xv[k][e], wv[e], a);
-          }
-          d[c] = a;
-        }
-      }
+      parity_logits<kMaxC>(xv, Wp, Bl, par, nc, d);                  // predict_head.hip's chain, per parity
       float m = 0.f;
       int bi = 0;
 #pragma unroll

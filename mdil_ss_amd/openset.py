@@ -70,9 +70,7 @@ def threshold_score(t):
     return code_floor(int(t)) if FINITE_CODES[0] <= t <= FINITE_CODES[1] else None
 
 
-def code_values(code):
-    """A stored code map as int64 (uint16 tensors support few operations)."""
-    return code.view(torch.int16).to(torch.int64) & 0xffff
+code_values = hc.q_values                       # a stored code map as int64
 
 
 def group_lut(unknown_ids=(), ignore_ids=()):
@@ -104,11 +102,7 @@ def kinds_mask(kinds):
 
 
 def check_nc(fn, nc):
-    nc = int(nc)
-    if not _openset_lib.MIN_CLASSES <= nc <= _openset_lib.MAX_CLASSES:
-        raise RuntimeError(f"mdil {fn}: {nc} classes (supported: {_openset_lib.MIN_CLASSES} to "
-                           f"{_openset_lib.MAX_CLASSES})")
-    return nc
+    return hc.check_nc(fn, _openset_lib, nc)
 
 
 # --------------------------------------------------------------------------------- entry points
@@ -160,7 +154,7 @@ def apply_counter_shapes(nc):
 
 def new_apply_counters(nc, dev):
     """The six int64 counters of ``openset_apply`` for ``nc`` classes, zeroed, on ``dev``."""
-    return {k: torch.zeros(s, dtype=torch.int64, device=dev) for k, s in apply_counter_shapes(nc).items()}
+    return hc.zero_counters(apply_counter_shapes(nc), dev)
 
 
 def check_thr(fn, thr):
@@ -187,8 +181,7 @@ def openset_apply(label, code, nc, thr, id_map=None, unknown_id=255, cdf=None, t
     lib = _openset_lib.load()
     nc = check_nc(fn, nc)
     thr = check_thr(fn, thr)
-    if not 0 <= int(unknown_id) <= 255:
-        raise RuntimeError(f"mdil {fn}: unknown_id {unknown_id} outside [0, 255]")
+    hc.check_id(fn, "unknown_id", unknown_id)
     hc.chk(fn, _PATH, label, "label", torch.uint8)
     hc.chk(fn, _PATH, code, "code", CODE)
     if label.numel() == 0 or label.shape != code.shape or label.device != code.device:
@@ -385,18 +378,6 @@ def _data_args(args, dataset, task, synthetic):
     return d
 
 
-def _image_batches(args, pool, dev):
-    from . import predict as P
-    files, stems = P._image_files(args.images)
-    for i in range(0, len(files), args.batch_size):
-        arrs = list(pool.map(lambda f: P._load_resized(f, args.height, args.width), files[i:i + args.batch_size]))
-        yield stems[i:i + args.batch_size], hc.image_batch(arrs, dev), None
-
-
-def _source_name(args):
-    return "images" if args.images else "synthetic" if args.synthetic else args.dataset
-
-
 def _score(args, model, dev, nc_data):
     foreign = bool(args.foreign_dataset or args.foreign_synthetic)
     void = nc_data - 1
@@ -418,7 +399,7 @@ def _score(args, model, dev, nc_data):
         for _, images, _ in rc.batches(f_args, args.num_classes[f_task], dev, score=False):
             meter.add(model, images, args.task, const_group=UNKNOWN)
             foreign_seen += images.shape[0]
-    report = {"mode": "score", "dataset": _source_name(args), "task": args.task, "data_task": args.data_task,
+    report = {"mode": "score", "dataset": rc.source_name(args), "task": args.task, "data_task": args.data_task,
               "images": images_seen, "unknown_ids": unknown_ids, "ignore_ids": list(args.ignore_ids)}
     if foreign:
         report.update(foreign_dataset="synthetic" if args.foreign_synthetic else args.foreign_dataset,
@@ -452,7 +433,7 @@ def _fit(args, model, dev, nc_data):
                      "rejected_known": int(known[t:].sum()), "cdf_starts": cdf_starts(cdf_lut(known))}
         print(f"{k:9s} reject code >= {t} (score >= {fitted[k]['threshold_score']}): "
               f"{fitted[k]['rejected_known']} of {fitted[k]['known_pixels']} known pixels")
-    report = {"mode": "fit", "dataset": _source_name(args), "task": args.task, "data_task": args.data_task, "images": n,
+    report = {"mode": "fit", "dataset": rc.source_name(args), "task": args.task, "data_task": args.data_task, "images": n,
               "known_fpr": args.known_fpr, "unknown_ids": unknown_ids, "ignore_ids": list(args.ignore_ids),
               "num_classes": args.num_classes[args.task], "nonfinite": meter.nonfinite(), "kinds": fitted}
     hc.write_json(report, args.fit)
@@ -488,10 +469,9 @@ def _write_maps(args, model, dev, nc):
     n = 0
     with hc.png_pool() as pool:
         png = hc.PngWriter(pool, args.out)
-        batches = _image_batches(args, pool, dev) if args.images else \
-            rc.batches(_data_args(args, None, args.data_task, args.synthetic), args.num_classes[args.data_task], dev,
-                       score=False)
-        for stems, images, _ in batches:
+        nc_data = None if args.images else args.num_classes[args.data_task]
+        for stems, images, _ in rc.image_or_dataset_batches(_data_args(args, None, args.data_task, args.synthetic), nc_data,
+                                                            pool, dev, score=False):
             label, code = meter.add(model, images, args.task, const_group=IGNORED, map_kind=args.kind, want_label=True)
             out, score = openset_apply(label, code, nc, thr, None, args.unknown_id, cdf, counters=some)
             planes = [out.unsqueeze(3), score.unsqueeze(3)]
@@ -507,7 +487,7 @@ def _write_maps(args, model, dev, nc):
             n += len(stems)
         png.wait()
     seen, rejected = counters["seen"].tolist(), counters["rejected"].tolist()
-    report = {"mode": "maps", "dataset": _source_name(args), "task": args.task, "images": n, "kind": args.kind,
+    report = {"mode": "maps", "dataset": rc.source_name(args), "task": args.task, "images": n, "kind": args.kind,
               "threshold_code": thr, "unknown_id": args.unknown_id, "seen": seen, "rejected": rejected,
               "rejected_share": sum(rejected) / max(1, sum(seen)), "nonfinite": meter.nonfinite(),
               "written": png.written}

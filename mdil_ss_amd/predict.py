@@ -94,7 +94,8 @@ def _load_resized(path, height, width):
 
 
 def _batches(args, nc, pool, dev):
-    """-> (stems, images f32 [n,3,H,W] on the device) per batch."""
+    """-> (stems, images f32 [n,3,H,W] on the device) per batch.  Not _report_common's feeder: this command
+    line has no dataset and no targets, and its procedural images come without their labels."""
     bs = args.batch_size
     if args.synthetic:
         from .dataset import ProceduralSeg
@@ -103,10 +104,7 @@ def _batches(args, nc, pool, dev):
             idx = range(i, min(i + bs, len(ds)))
             yield [f"synthetic_{j:04d}" for j in idx], torch.stack([ds[j][0] for j in idx]).to(dev)
         return
-    files, stems = _image_files(args.images)
-    for i in range(0, len(files), bs):
-        arrs = list(pool.map(lambda f: _load_resized(f, args.height, args.width), files[i:i + bs]))
-        yield stems[i:i + bs], hc.image_batch(arrs, dev)
+    yield from hc.image_batches(args, pool, dev)
 
 
 def main(args):

@@ -31,29 +31,16 @@ APPLY_COUNTERS = ("seen", "kept", "confusion", "bad_targets", "bad_labels")
 DEFAULT_PORTION = 0.2
 
 
-def q_values(qconf):
-    """The stored confidences as int64 (uint16 tensors support few operations)."""
-    return qconf.view(torch.int16).to(torch.int64) & 0xffff
+q_values = hc.q_values                          # the stored confidences as int64
 
 
 def check_nc(fn, nc):
-    nc = int(nc)
-    if not _pseudo_lib.MIN_CLASSES <= nc <= _pseudo_lib.MAX_CLASSES:
-        raise RuntimeError(f"mdil {fn}: {nc} classes (supported: {_pseudo_lib.MIN_CLASSES} to "
-                           f"{_pseudo_lib.MAX_CLASSES})")
-    return nc
+    return hc.check_nc(fn, _pseudo_lib, nc)
 
 
 def check_thr(fn, thr, nc):
     """-> the thresholds as a list of nc ints in [0, 65536]."""
-    try:
-        t = [int(v) for v in (thr.tolist() if isinstance(thr, torch.Tensor) else thr)]
-    except (TypeError, ValueError):
-        raise RuntimeError(f"mdil {fn}: thr must be {nc} integers, got {thr!r}") from None
-    if len(t) != nc or any(v < 0 or v > Q_ONE for v in t):
-        raise RuntimeError(f"mdil {fn}: thr must be {nc} integers in [0, {Q_ONE}] (the pseudo-label path keeps a "
-                           f"pixel of class c when q >= thr[c]), got {t}")
-    return t
+    return hc.check_q_thresholds(fn, thr, nc, Q_ONE, "the pseudo-label path keeps a pixel of class c when q >= thr[c]")
 
 
 def check_portion(portion, nc):
@@ -136,8 +123,7 @@ def pseudo_refine(label, qconf, nc, sel, hist2, bad_labels):
 
 def new_apply_counters(nc, dev):
     """The five int64 counters of ``pseudo_apply`` for ``nc`` classes, zeroed, on ``dev``."""
-    shapes = apply_counter_shapes(nc)
-    return {k: torch.zeros(shapes[k], dtype=torch.int64, device=dev) for k in APPLY_COUNTERS}
+    return hc.zero_counters(apply_counter_shapes(nc), dev)
 
 
 def apply_counter_shapes(nc):
@@ -159,8 +145,7 @@ def pseudo_apply(label, qconf, nc, thr, id_map=None, drop_id=255, target=None, i
     on_device = isinstance(thr, torch.Tensor) and thr.is_cuda
     if not on_device:
         thr = check_thr(fn, thr, nc)
-    if not 0 <= int(drop_id) <= 255:
-        raise RuntimeError(f"mdil {fn}: drop_id {drop_id} outside [0, 255]")
+    hc.check_id(fn, "drop_id", drop_id)
     hc.check_ignore_index(fn, ignore_index)
     _maps(fn, label, qconf)
     dev = label.device
@@ -393,18 +378,6 @@ def plan_tree(args, files):
     return labels, names
 
 
-def _batches(args, nc, pool, dev):
-    """-> (stems, images f32 [n,3,H,W], target u8 [n,H,W] or None) per batch, on the device."""
-    if args.images:
-        from . import predict as P
-        files, stems = P._image_files(args.images)
-        for i in range(0, len(files), args.batch_size):
-            arrs = list(pool.map(lambda f: P._load_resized(f, args.height, args.width), files[i:i + args.batch_size]))
-            yield stems[i:i + args.batch_size], hc.image_batch(arrs, dev), None
-        return
-    yield from rc.batches(args, nc, dev, score=True, unique_stems=bool(args.out))
-
-
 def main(args):
     _refusals(args)
     rc.refuse_task(args.task, args.num_classes)
@@ -420,7 +393,7 @@ def main(args):
     meter = PseudoLabeller(nc, args.store_gb)
     stems, targets = [], []
     with hc.png_pool() as pool:
-        for s, images, target in _batches(args, nc, pool, dev):
+        for s, images, target in rc.image_or_dataset_batches(args, nc, pool, dev, unique_stems=bool(args.out)):
             meter.add(model, images, args.task)
             stems.extend(s)
             if target is not None:
@@ -450,8 +423,7 @@ def main(args):
                 pass
             everything = meter.counters
     seen, kept = counters["seen"].tolist(), counters["kept"].tolist()
-    report = {"dataset": "images" if args.images else "synthetic" if args.synthetic else args.dataset,
-              "task": args.task, "images": len(stems), "written": png.written, "portion": portion, "floor": args.floor,
+    report = {"dataset": rc.source_name(args), "task": args.task, "images": len(stems), "written": png.written, "portion": portion, "floor": args.floor,
               "seen": seen, "kept": kept, "thr": thr, "thr_probability": [t / Q_ONE for t in thr], "k": k,
               "kept_share": sum(kept) / max(1, sum(seen)), "nonfinite": meter.nonfinite(),
               "hist": hist.tolist()}

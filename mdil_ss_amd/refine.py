@@ -194,18 +194,6 @@ def params_of(args):
                         args.theta_alpha, args.theta_beta, args.theta_gamma)
 
 
-def _batches(args, nc, pool, dev):
-    """-> (stems, images f32 [n,3,H,W], target u8 [n,H,W] or None) per batch, on the device."""
-    if args.images:
-        from . import predict as P
-        files, stems = P._image_files(args.images)
-        for i in range(0, len(files), args.batch_size):
-            arrs = list(pool.map(lambda f: P._load_resized(f, args.height, args.width), files[i:i + args.batch_size]))
-            yield stems[i:i + args.batch_size], hc.image_batch(arrs, dev), None
-        return
-    yield from rc.batches(args, nc, dev, score=args.score, unique_stems=bool(args.out))
-
-
 def main(args):
     _refusals(args)
     rc.refuse_task(args.task, args.num_classes)
@@ -221,7 +209,7 @@ def main(args):
     images_seen = 0
     with hc.png_pool() as pool:
         png = hc.PngWriter(pool, args.out)
-        for stems, images, target in _batches(args, nc, pool, dev):
+        for stems, images, target in rc.image_or_dataset_batches(args, nc, pool, dev, args.score, bool(args.out)):
             label, conf, _ = meter.add(model, images, args.task, params, target, want_confidence=args.confidence)
             images_seen += len(stems)
             if not args.out:
@@ -242,7 +230,7 @@ def main(args):
                 if conf is not None:
                     png.submit(host[k, :, :, c], f"{stem}_conf.png")
         png.wait()
-    report = {"dataset": "images" if args.images else "synthetic" if args.synthetic else args.dataset,
+    report = {"dataset": rc.source_name(args),
               "task": args.task, "images": images_seen, "written": png.written, "params": params._asdict()}
     scored = meter.report()
     report.update({k: scored[k] for k in ("pixels", "changed", "changed_share")})

@@ -265,18 +265,6 @@ class Router:
 
 
 # ------------------------------------------------------------------------------------------ CLI
-def _batches(args, pool, dev):
-    """-> (stems, images f32 [n,3,H,W], target u8 [n,H,W] or None) per batch, on the device."""
-    if args.images:
-        from . import predict as P
-        files, stems = P._image_files(args.images)
-        for i in range(0, len(files), args.batch_size):
-            arrs = list(pool.map(lambda f: P._load_resized(f, args.height, args.width), files[i:i + args.batch_size]))
-            yield stems[i:i + args.batch_size], hc.image_batch(arrs, dev), None
-        return
-    yield from rc.batches(args, args.num_classes[args.task], dev, score=args.score, unique_stems=bool(args.out))
-
-
 def main(args):
     _refusals(args)
     from .fullres import iou_rule
@@ -295,7 +283,8 @@ def main(args):
         unscored = 0
     with hc.png_pool() as pool:
         png = hc.PngWriter(pool, args.out)
-        for stems, images, target in _batches(args, pool, dev):
+        nc_data = None if args.images else args.num_classes[args.task]   # a dataset is read in --task's label space
+        for stems, images, target in rc.image_or_dataset_batches(args, nc_data, pool, dev, args.score, bool(args.out)):
             routed = router.route(images)
             tasks, label, scores = routed["tasks"], routed["label"], routed["scores"].cpu().tolist()
             nonfinite += routed["nonfinite"]
@@ -327,7 +316,7 @@ def main(args):
                     if args.colour:
                         png.submit(host[k, :, :, 1:4], f"{stem}_colour.png")
         png.wait()
-    report = {"dataset": "images" if args.images else "synthetic" if args.synthetic else args.dataset, "by": args.by,
+    report = {"dataset": rc.source_name(args), "by": args.by,
               "tasks": router.tasks, "images": len(per_image), "routes": per_image,
               "sent": {str(t): n for t, n in sent.items()}, "nonfinite": nonfinite, "written": png.written}
     print(f"{report['dataset']}: {len(per_image)} images routed by {args.by}: " +

@@ -200,12 +200,169 @@ def cases():
     return out
 
 
-def record(path):
+# ------------------------------------------------------------------------- the map add-ons
+def _poison(x):
+    """One NaN and one +inf feature, in two different pixels."""
+    x = x.clone()
+    x[0, 0, 1, 3] = float("nan")
+    x[0, x.shape[1] - 1, x.shape[2] // 2, 7] = float("inf")
+    return x
+
+
+def _head_inputs(nc, shape, seed, poison):
+    """``_inputs`` for one feature tensor, on the host, with the target of its label grid."""
+    (x,), w, b, ids, _, g = _inputs(nc, [shape], seed)
+    target = _target(nc, (shape[0], 2 * shape[1], 2 * shape[2]), g)
+    return (_poison(x) if poison else x), w, b, ids, target, g
+
+
+def _zeros(dev, *shape):
+    return torch.zeros(*shape, dtype=torch.int64, device=dev)
+
+
+def _prefixed(prefix, tensors):
+    return {f"{prefix}_{k}": _digest(v) for k, v in tensors.items()}
+
+
+def _pseudo(dev, nc, shape, seed, poison=False):
+    from mdil_ss_amd import pseudo as P
+    x, w, b, ids, target, g = _head_inputs(nc, shape, seed, poison)
+    hist, nonfinite = _zeros(dev, nc, 256), _zeros(dev, 1)
+    label, qconf = P.pseudo_head(x.to(dev), w.to(dev), b.to(dev), hist, nonfinite)
+    sel = hist.cpu().argmax(1).tolist()                  # per class the fullest high byte
+    hist2, bad_labels = _zeros(dev, nc, 256), _zeros(dev, 1)
+    P.pseudo_refine(label, qconf, nc, sel, hist2, bad_labels)
+    thr = torch.randint(0, P.Q_ONE + 1, (nc,), generator=g).tolist()
+    counters = P.new_apply_counters(nc, dev)
+    out = P.pseudo_apply(label, qconf, nc, thr, ids.to(dev), 255, target.to(dev), IGNORE, counters)
+    d = {"label": _digest(label), "qconf": _digest(qconf), "hist": _digest(hist), "nonfinite": _digest(nonfinite),
+         "hist2": _digest(hist2), "refine_bad_labels": _digest(bad_labels), "out": _digest(out)}
+    d.update(_prefixed("apply", counters))
+    return d
+
+
+def _openset(dev, nc, shape, seed, poison=False):
+    from mdil_ss_amd import openset as O
+    x, w, b, ids, target, g = _head_inputs(nc, shape, seed, poison)
+    lut = O.group_lut(unknown_ids=[1], ignore_ids=[IGNORE]).to(dev)
+    target = target.to(dev)
+    hist, nonfinite = _zeros(dev, len(O.KINDS), 2, O.CODES), _zeros(dev, 1)
+    label, code = O.openset_head(x.to(dev), w.to(dev), b.to(dev), target, lut, kinds=O.KINDS, map_kind="entropy",
+                                 hist=hist, nonfinite=nonfinite)
+    thr = int(O.code_values(code).median())              # rejects about half of the pixels
+    cdf = O.cdf_lut(hist[O.KINDS.index("entropy"), O.KNOWN].cpu()).to(dev)
+    counters = O.new_apply_counters(nc, dev)
+    out, score = O.openset_apply(label, code, nc, thr, ids.to(dev), 255, cdf, target, lut, counters)
+    d = {"label": _digest(label), "code": _digest(code), "hist": _digest(hist), "nonfinite": _digest(nonfinite),
+         "out": _digest(out), "score": _digest(score)}
+    d.update(_prefixed("apply", counters))
+    return d
+
+
+def _audit(dev, nc, shape, seed, poison=False):
+    from mdil_ss_amd import audit as A
+    x, w, b, _, target, g = _head_inputs(nc, shape, seed, poison)
+    x, w, b, target = (t.to(dev) for t in (x, w, b, target))
+    N = shape[0]
+    first = A.new_head_counters(nc, N, dev, ("count", "qsum", "bad_targets", "nonfinite"))
+    A.audit_head(x, w, b, target, IGNORE, counters=first)
+    thr = A.thresholds(first["count"].cpu(), first["qsum"].cpu())
+    second = A.new_head_counters(nc, N, dev)
+    qmap, suggest = A.audit_head(x, w, b, target, IGNORE, thr, A.GIVEN, 255, second, want_suggest=True)
+    max_q = torch.randint(-1, A.Q_ONE, (nc,), generator=g).tolist()
+    d = {"qmap": _digest(qmap), "suggest": _digest(suggest)}
+    d.update(_prefixed("sweep1", first))
+    d.update(_prefixed("sweep2", second))
+    for mode in A.MODES:
+        counters = A.new_apply_counters(nc, dev)
+        out, mask = A.audit_apply(target, suggest, qmap, nc, max_q, mode, IGNORE, 255, 255, counters, want_mask=True)
+        d.update({f"{mode}_out": _digest(out), f"{mode}_mask": _digest(mask)})
+        d.update(_prefixed(mode, counters))
+    return d
+
+
+ACQUIRE_TILE = (4, 6)                                    # ragged on every shape here; a work-group spans several
+
+
+def _acquire(dev, nc, shape, seed, poison=False):
+    from mdil_ss_amd import acquire as Q
+    x, w, b, _, target, g = _head_inputs(nc, shape, seed, poison)
+    x, w, b, target = (t.to(dev) for t in (x, w, b, target))
+    N, size = shape[0], (2 * shape[1], 2 * shape[2])
+    d = {}
+    for kind in Q.KINDS:
+        tiles = Q.new_tiles(N, size, ACQUIRE_TILE, nc, dev)
+        counters = {k: _zeros(dev, 1) for k in Q.HEAD_COUNTERS}
+        label, qmap = Q.acquire_head(x, w, b, ACQUIRE_TILE, kind, target, IGNORE, tiles, counters, want_label=True,
+                                     want_qmap=True)
+        d.update({f"{kind}_label": _digest(label), f"{kind}_qmap": _digest(qmap), f"{kind}_tiles": _digest(tiles)})
+        d.update(_prefixed(kind, counters))
+    selected = (torch.rand((N,) + Q.tile_grid(size, ACQUIRE_TILE), generator=g) < 0.4).to(torch.uint8)
+    previous, fill = (_target(nc, (N,) + size, g) for _ in range(2))
+    counters = Q.new_apply_counters(nc, dev)
+    out, mask = Q.acquire_apply(selected.to(dev), size, ACQUIRE_TILE, nc, target, previous.to(dev), fill.to(dev), IGNORE,
+                                255, counters, want_mask=True)
+    d.update({"out": _digest(out), "mask": _digest(mask)})
+    d.update(_prefixed("apply", counters))
+    return d
+
+
+def _route(dev, nc, shape, seed, poison=False):
+    from mdil_ss_amd import route as R
+    x, w, b, _, _, _ = _head_inputs(nc, shape, seed, poison)
+    nonfinite = _zeros(dev, shape[0])
+    out = R.route_head(x.to(dev), w.to(dev), b.to(dev), label=True, maps=True, scores=True, nonfinite=nonfinite)
+    d = {k: _digest(v) for k, v in out.items()}
+    d["nonfinite"] = _digest(nonfinite)
+    return d
+
+
+def _stem(dev, shape, seed, poison=False):
+    from mdil_ss_amd import route as R
+    g = torch.Generator().manual_seed(seed)
+    images = torch.rand(shape, generator=g)
+    w = torch.randn(R.STEM_CHANNELS - 3, 3, 3, 3, generator=g) * 0.3
+    b = torch.randn(R.STEM_CHANNELS - 3, generator=g) * 0.2
+    if poison:
+        images[0, 1, 2, 5] = float("nan")
+        images[0, 2, shape[2] - 1, 0] = float("inf")
+    nonfinite = _zeros(dev, shape[0])
+    moments, act = R.stem_moments(images.to(dev), w.to(dev), b.to(dev), act=True, nonfinite=nonfinite)
+    return {"moments": _digest(moments), "act": _digest(act), "nonfinite": _digest(nonfinite)}
+
+
+MAP_GOLDEN = os.path.join(REPO, "tests", "golden", "map_addon_bytes.json")
+# 513 x 1023 feature pixels: past 768 x 256 and 256 x 1024 of them, so every head's loop strides, and its
+# 1026 x 2046 label grid is past the 512 x 256 x 8 pixels of the map kernels' grid
+MAP_GRID = (1, 513, 1023)
+STEM_SMALL, STEM_GRID = (1, 3, 18, 14), (1, 3, 514, 514)   # 257 x 257 positions: past 256 x 256 of one image
+
+
+def map_cases():
+    """{name: run(dev) -> {buffer: sha256}} of the map add-ons (pseudo, openset, audit, acquire, route): every
+    output map and every counter of their eleven kernels, recorded in MAP_GOLDEN from the kernel sources as
+    they were BEFORE these add-ons came to share mdil_ss_amd/ext/map_common.h."""
+    out = {}
+    runs = (("pseudo", _pseudo, 1000), ("openset", _openset, 1100), ("audit", _audit, 1200),
+            ("acquire", _acquire, 1300), ("route", _route, 1400))
+    for tag, run, seed in runs:
+        for nc in CLASSES:
+            out[f"{tag}-nc{nc}"] = lambda dev, run=run, nc=nc, seed=seed: run(dev, nc, SMALL, seed + nc)
+        out[f"{tag}-several"] = lambda dev, run=run, seed=seed: run(dev, SEVERAL_NC, SEVERAL, seed + 40)
+        out[f"{tag}-grid"] = lambda dev, run=run, seed=seed: run(dev, 2, MAP_GRID, seed + 50)
+        out[f"{tag}-nonfinite"] = lambda dev, run=run, seed=seed: run(dev, 20, SMALL, seed + 60, poison=True)
+    out["stem-small"] = lambda dev: _stem(dev, STEM_SMALL, 1500)
+    out["stem-grid"] = lambda dev: _stem(dev, STEM_GRID, 1501)
+    out["stem-nonfinite"] = lambda dev: _stem(dev, STEM_SMALL, 1502, poison=True)
+    return out
+
+
+def record(path, table=cases):
     sys.path.insert(0, REPO)
     import mdil_ss_amd  # noqa: F401
     assert torch.cuda.is_available(), "recording needs an MI355X"
     dev = torch.device("cuda", 0)
-    digests = {name: run(dev) for name, run in cases().items()}
+    digests = {name: run(dev) for name, run in table().items()}
     with open(path, "w") as f:
         json.dump(digests, f, indent=1, sort_keys=True)
         f.write("\n")
@@ -213,4 +370,4 @@ def record(path):
 
 
 if __name__ == "__main__":
-    record(sys.argv[1])
+    record(sys.argv[1], map_cases if sys.argv[2:] == ["map"] else cases)
