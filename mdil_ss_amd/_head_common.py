@@ -1,9 +1,9 @@
 """What the head drivers share (predict.py, fullres.py, ensemble.py and, with _report_common.py on
 top, drift.py, calibrate.py, boundary.py, pseudo.py, route.py, segments.py, refine.py, significance.py,
-openset.py, audit.py and acquire.py; latent.py and similarity.py take the loader and the parser): the
+openset.py, audit.py, acquire.py and ripu.py; latent.py and similarity.py take the loader and the parser): the
 argument checks of their entry points -- each takes the entry point's name, so every message reads
 as it always did -- the 16-bit map, threshold and counter helpers of the map add-ons (pseudo,
-openset, audit, acquire), the checkpoint loader, the image folder -> image tensor steps, the bounded
+openset, audit, acquire, ripu), the checkpoint loader, the image folder -> image tensor steps, the bounded
 PNG writer and the score report of the inference command lines."""
 import json
 import os

@@ -1,8 +1,8 @@
 """What the report drivers (drift.py, calibrate.py, similarity.py, boundary.py, pseudo.py, route.py,
-segments.py, refine.py, significance.py, openset.py, audit.py, acquire.py) share on top of
+segments.py, refine.py, significance.py, openset.py, audit.py, acquire.py, ripu.py) share on top of
 _head_common.py: the network-size batch feeders (a dataset, or a folder of images), the counter and
 workspace checks of the entry points, the workspace, source and bad-target steps of the meters, the
-label tree that audit and acquire write, and the flags and refusals of the command lines.  Plain
+label tree that audit, acquire and ripu write, and the flags and refusals of the command lines.  Plain
 functions; each takes the caller's name where a message carries it, so every message reads as it
 always did."""
 import os
