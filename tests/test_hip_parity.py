@@ -462,7 +462,11 @@ def test_fused_head_and_loss(dev, nc, N, H, W):
     consumes its logits (models/erfnet_RA_parallel.py:179-180,188 + train_new_task_step2.py:84-92,
     241,293-297), logits never materialised, backward recomputes them -- against stock torch:
     conv_transpose2d + the oracle's losses + autograd.  Pixel counts that are not multiples of the
-    64-pixel wave batch; ignore labels; an upstream gradient scale; the optional logits output."""
+    64-pixel wave batch; ignore labels; an upstream gradient scale; the optional logits output.
+    (At most 2,304 feature pixels: every wave runs ONE tile here.  Past the grid bound of 65,536 pixels --
+    several tiles per wave, the ragged tile in a later round, the reduce kernel over more than 64 partial
+    rows -- the head, the unfused losses, the pool kernels and Adam are compared with float64 references
+    in tests/test_grid_rounds_gpu.py.)"""
     from mdil_ss_amd import ops
     g = torch.Generator().manual_seed(10 * nc + H)
     w = (torch.randn(16, nc, 2, 2, generator=g) * 0.3).requires_grad_(True)
