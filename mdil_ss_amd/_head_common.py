@@ -4,7 +4,8 @@ openset.py, audit.py, acquire.py and ripu.py; latent.py and similarity.py take t
 argument checks of their entry points -- each takes the entry point's name, so every message reads
 as it always did -- the 16-bit map, threshold and counter helpers of the map add-ons (pseudo,
 openset, audit, acquire, ripu), the checkpoint loader, the image folder -> image tensor steps, the bounded
-PNG writer and the score report of the inference command lines."""
+PNG writer and the score report of the inference command lines.  _annotate_common.py builds the label
+tree writer of audit, acquire and ripu on ``PngWriter`` and ends their ``main`` with ``write_json``."""
 import json
 import os
 from argparse import ArgumentParser

@@ -4,7 +4,8 @@ _head_common.py: the network-size batch feeders (a dataset, or a folder of image
 workspace checks of the entry points, the workspace, source and bad-target steps of the meters, the
 label tree that audit, acquire and ripu write, and the flags and refusals of the command lines.  Plain
 functions; each takes the caller's name where a message carries it, so every message reads as it
-always did."""
+always did.  What only the annotator family (audit, acquire, ripu) shares -- its refusals and flags, the
+writer of that label tree, the annotated block of the report -- is one level up, in _annotate_common.py."""
 import os
 
 import torch

@@ -27,12 +27,13 @@ which criterion finds the errors of a trained head on BDD or IDD.  The fixed til
 of RIPU's sliding (2k+1)^2 neighbourhood, which is not built.  No retraining on the selected labels is run."""
 import json
 import math
-import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import _acquire_lib
+from . import _annotate_common as ac
 from . import _head_common as hc
 from . import _report_common as rc
 
@@ -50,6 +51,7 @@ _M64 = (1 << 64) - 1
 
 q_values = hc.q_values                          # a stored q map as int64
 check_id = hc.check_id
+_read_labels = ac.read_labels
 
 
 def check_nc(fn, nc):
@@ -291,25 +293,6 @@ def plan_label_tree(args):
     return rc.plan_label_tree(args, args.out_root)
 
 
-def _read_labels(root, layout, subset, names, size, what):
-    """The label files ``names`` of a tree written by ``--out-root`` -> u8 [n, Hl, Wl] (host)."""
-    from PIL import Image
-    from . import pseudo as P
-    folder = os.path.join(root, P.LAYOUTS[layout][1], subset)
-    maps = []
-    for name in names:
-        path = os.path.join(folder, name)
-        if not os.path.isfile(path):
-            raise RuntimeError(f"{what} {root}: no label file {path}")
-        with Image.open(path) as im:
-            arr = np.array(im, dtype=np.uint8)
-        if arr.shape != tuple(size):
-            raise RuntimeError(f"{what} {root}: {path} is {arr.shape[0]} x {arr.shape[1]}, the network's labels are "
-                               f"{size[0]} x {size[1]}")
-        maps.append(arr)
-    return torch.from_numpy(np.stack(maps))
-
-
 def read_selection(path, tile, size):
     """A ``selection.json`` of an earlier round -> {stem: set of (ty, tx)}."""
     with open(path) as f:
@@ -328,246 +311,158 @@ def error_recall(table, chosen):
     return int(table[chosen, 2].sum()) / wrong if wrong else 0.0
 
 
-def main(args):
-    _refusals(args)
-    rc.refuse_task(args.task, args.num_classes)
-    for flag, path in (("--previous", args.previous),):
-        if path and not os.path.isfile(path):
-            raise RuntimeError(f"{flag} {path}: no such file")
-    for flag, path in (("--previous-root", args.previous_root), ("--fill-root", args.fill_root)):
-        if path and not os.path.isdir(path):
-            raise RuntimeError(f"{flag} {path}: no such folder")
-    dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
-    ignore = nc - 1                                    # the trainers' relabelled ignore class
-    tile = check_tile("acquire", args.tile)
-    size = (args.height, args.width)
-    labelled = not args.images
+def _table_pass(args, head, tile, pool):
+    """Pass 1: the tile table of every image, kept on the host -> (table [tiles, 4 + nc], stems, given, nonfinite)."""
+    nc, names = head.nc, HEAD_COUNTERS if head.labelled else ("nonfinite",)
+    counters = hc.zero_counters(dict.fromkeys(HEAD_COUNTERS, (1,)), head.dev, names)
+    tables, stems, given = [], [], torch.zeros(nc, dtype=torch.int64, device=head.dev)
+    for s, images, target in ac.batches(args, head, pool):
+        t = new_tiles(images.shape[0], head.size, tile, nc, head.dev)
+        acquire_head(ac.features(head, images), head.w, head.b, tile, args.kind, target, head.ign, t, counters)
+        tables.append(t.cpu())
+        stems.extend(s)
+        ac.given_counts(given, target, nc, head.ignore)
+    if head.labelled:
+        rc.refuse_bad_targets("acquire", counters, nc, head.ignore)
+    return torch.cat(tables).reshape(-1, FIELDS + nc), stems, given, int(counters["nonfinite"].item())
+
+
+def _split(args, table, stems, tile, size):
+    """Every tile of the split: its image, its index and place in it, its size, and whether it may be chosen."""
     Ty, Tx = tile_grid(size, tile)
     boxes, box_pixels = tile_boxes(size, tile)
-    w, b = (t.detach() for t in model.head_params(args.task))
-    head_counters = {k: torch.zeros(1, dtype=torch.int64, device=dev) for k in (HEAD_COUNTERS if labelled else
-                                                                                   ("nonfinite",))}
+    M, T = len(stems), Ty * Tx
+    tidx = np.tile(np.arange(T), M)
+    usable = table[:, 0].numpy() > 0
+    if args.previous:
+        before = read_selection(args.previous, tile, size)
+        for i, stem in enumerate(stems):
+            for (y, x) in before.get(stem, ()):
+                if y < Ty and x < Tx:
+                    usable[i * T + y * Tx + x] = False
+    total = M * size[0] * size[1]
+    return SimpleNamespace(M=M, T=T, grid=(Ty, Tx), boxes=boxes, image=np.repeat(np.arange(M), T), tidx=tidx, ty=tidx // Tx,
+                           tx=tidx % Tx, pixels=np.tile(np.asarray(box_pixels), M), image_pixels=[size[0] * size[1]] * M,
+                           total=total, budget_pixels=args.budget * total, usable=usable)
 
-    def features(images):
-        with torch.no_grad():
-            return model.features(images, args.task).contiguous()
 
-    # ---- pass 1: the tile table of every image, kept on the host
-    tables, stems, given = [], [], torch.zeros(nc, dtype=torch.int64, device=dev)
+def _choose(args, table, sp, by, labelled):
+    """Ranks the split's tiles by ``by`` and takes them within the budget -> (scores, chosen in rank order, pixels)."""
+    scores = tile_scores(table, by, sp.image, sp.tidx, args.seed, labelled).numpy()
+    order = rank_tiles(scores, sp.image, sp.ty, sp.tx, sp.usable)
+    return (scores,) + select_tiles(order, sp.pixels, sp.image, sp.image_pixels, sp.budget_pixels, args.max_per_image)
+
+
+def _report(args, head, table, stems, sp, tile, scores, chosen, spent, nonfinite):
+    """-> (the report without what pass 2 adds, selection.json, the images with a selected tile)"""
+    nc, size, M, image = head.nc, head.size, sp.M, sp.image
+    touched = sorted({int(image[i]) for i in chosen})
+    per_stem = {}
+    for i in chosen:                                   # in rank order
+        per_stem.setdefault(stems[int(image[i])], []).append(list(sp.boxes[int(sp.tidx[i])]) + [float(scores[i])])
+    selection = {"tile": list(tile), "size": list(size), "kind": args.kind, "by": args.by, "budget": args.budget,
+                 "seed": args.seed, "tiles": per_stem}
+    U, I = uncertainty_of(table), impurity_of(table)
+    sel_idx = torch.tensor(chosen, dtype=torch.long)
+    live = torch.from_numpy(table[:, 0].numpy() > 0)
+    hist_all, hist_sel = table[:, FIELDS:].sum(0), table[sel_idx, FIELDS:].sum(0)
+    per_image_tiles = np.bincount(image[chosen], minlength=M) if chosen else np.zeros(M, dtype=np.int64)
+    report = {"dataset": rc.source_name(args), "subset": args.subset, "task": args.task, "num_classes": nc,
+              "kind": args.kind, "by": args.by, "tile": list(tile), "size": list(size), "budget": args.budget,
+              "max_per_image": args.max_per_image, "seed": args.seed, "images": M, "total_pixels": sp.total,
+              "pixels_asked": sp.budget_pixels, "pixels_spent": spent, "spent_share": spent / sp.total,
+              "tiles": int(M * sp.T), "tiles_selected": len(chosen), "images_touched": len(touched),
+              "tiles_per_image_mean": len(chosen) / max(1, len(touched)), "tiles_per_image_max": int(per_image_tiles.max()),
+              "mean_uncertainty_selected": float(U[sel_idx].mean()) if chosen else 0.0,
+              "mean_uncertainty_all": float(U[live].mean()) if bool(live.any()) else 0.0,
+              "mean_impurity_selected": float(I[sel_idx].mean()) if chosen else 0.0,
+              "mean_impurity_all": float(I[live].mean()) if bool(live.any()) else 0.0,
+              "predicted_selected": hist_sel.tolist(), "predicted_all": hist_all.tolist(),
+              "nonfinite": nonfinite, "previous": args.previous}
+    if head.labelled:
+        recall = {by: error_recall(table, torch.tensor(_choose(args, table, sp, by, True)[1], dtype=torch.long))
+                  for by in CRITERIA}
+        report.update(error_recall=recall, error_recall_chosen=error_recall(table, sel_idx),
+                      wrong_pixels=int(table[:, 2].sum()), valid_pixels=int(table[:, 3].sum()))
+    return report, selection, touched
+
+
+def _write_pass(args, head, tile, pool, sp, chosen, touched, given):
+    """Pass 2, over the images with a selected tile (every image where an earlier round or fill labels come in):
+    ``acquire_apply``, the maps of ``--out`` and the tree of ``--out-root`` -> (what the report gains, the paths)"""
+    nc, size, dev = head.nc, head.size, head.dev
+    selected = torch.zeros((sp.M,) + sp.grid, dtype=torch.uint8)
+    selected.view(-1)[torch.tensor(chosen, dtype=torch.long)] = 1
+    everywhere, touched = bool(args.previous_root or args.fill_root), set(touched)
+    counters = new_apply_counters(nc, dev, APPLY_COUNTERS if head.labelled else ("shown", "kept", "filled"))
+    writer = ac.LabelTreeWriter(pool, args, "--out-root", args.out_root, args.out, sp.M)
+    for s, images, target in ac.batches(args, head, pool):
+        i0 = writer.seen
+        idx = [j for j in range(len(s)) if everywhere or (i0 + j) in touched]
+        writer.wait()
+        out = None
+        if idx:
+            pick = torch.tensor(idx, dtype=torch.long, device=dev)
+            sel = selected[[i0 + j for j in idx]].contiguous().to(dev)
+            prev, fill = writer.earlier_labels(args, idx, size, dev)
+            tgt = target[pick].contiguous() if target is not None else None
+            out, mask = acquire_apply(sel, size, tile, nc, tgt, prev, fill, head.ign, 255, counters,
+                                      want_out=bool(args.out_root), want_mask=bool(args.out))
+            if args.out:
+                _, qmap = acquire_head(ac.features(head, images[pick].contiguous()), head.w, head.b, tile, args.kind,
+                                       want_qmap=True)
+                writer.write_maps([s[j] for j in idx], select=mask, uncertainty=(q_values(qmap) >> 8).to(torch.uint8))
+        writer.write_batch(s, images, out, head.ignore, idx)
+    written = writer.close()
+    c = {k: v.cpu() for k, v in counters.items()}
+    gained = dict(shown=int(c["shown"]), kept=c["kept"].tolist(), filled=c["filled"].tolist())
+    if head.labelled:
+        gained.update(ac.annotated_block("acquire", c, given, nc))
+    return gained, written
+
+
+def main(args):
+    _refusals(args)
+    head = ac.open_head(args)
+    tile = check_tile("acquire", args.tile)
+    written = []
     with hc.png_pool() as pool:
-        for s, images, target in rc.image_or_dataset_batches(args, nc, pool, dev, unique_stems=True):
-            if tuple(images.shape[2:]) != size:
-                raise RuntimeError(f"images of {tuple(images.shape[2:])}, expected {size}")
-            t = new_tiles(images.shape[0], size, tile, nc, dev)
-            acquire_head(features(images), w, b, tile, args.kind, target, ignore if labelled else -1, t, head_counters)
-            tables.append(t.cpu())
-            stems.extend(s)
-            if target is not None:
-                tl = target.reshape(-1).long()
-                given += torch.bincount(tl[(tl < nc) & (tl != ignore)], minlength=nc)
-        if labelled:
-            rc.refuse_bad_targets("acquire", head_counters, nc, ignore)
-        table = torch.cat(tables).reshape(-1, FIELDS + nc)
-        M, T = len(stems), Ty * Tx
-        image = np.repeat(np.arange(M), T)
-        tidx = np.tile(np.arange(T), M)
-        ty, tx = tidx // Tx, tidx % Tx
-        pixels = np.tile(np.asarray(box_pixels), M)
-        image_pixels = [size[0] * size[1]] * M
-        total = M * size[0] * size[1]
-        budget_pixels = args.budget * total
-        usable = table[:, 0].numpy() > 0
-        if args.previous:
-            before = read_selection(args.previous, tile, size)
-            for i, stem in enumerate(stems):
-                for (y, x) in before.get(stem, ()):
-                    if y < Ty and x < Tx:
-                        usable[i * T + y * Tx + x] = False
-
-        def choose(by):
-            scores = tile_scores(table, by, image, tidx, args.seed, labelled).numpy()
-            order = rank_tiles(scores, image, ty, tx, usable)
-            chosen, spent = select_tiles(order, pixels, image, image_pixels, budget_pixels, args.max_per_image)
-            return scores, chosen, spent
-
-        scores, chosen, spent = choose(args.by)
-        selected = torch.zeros(M, Ty, Tx, dtype=torch.uint8)
-        selected.view(-1)[torch.tensor(chosen, dtype=torch.long)] = 1
-        touched = sorted({int(image[i]) for i in chosen})
-        per_stem = {}
-        for i in chosen:                                   # in rank order
-            per_stem.setdefault(stems[int(image[i])], []).append(list(boxes[int(tidx[i])]) + [float(scores[i])])
-        selection = {"tile": list(tile), "size": list(size), "kind": args.kind, "by": args.by, "budget": args.budget,
-                     "seed": args.seed, "tiles": per_stem}
-
-        U, I = uncertainty_of(table), impurity_of(table)
-        sel_idx = torch.tensor(chosen, dtype=torch.long)
-        live = torch.from_numpy(table[:, 0].numpy() > 0)
-        hist_all, hist_sel = table[:, FIELDS:].sum(0), table[sel_idx, FIELDS:].sum(0)
-        per_image_tiles = np.bincount(image[chosen], minlength=M) if chosen else np.zeros(M, dtype=np.int64)
-        report = {"dataset": rc.source_name(args), "subset": args.subset, "task": args.task, "num_classes": nc,
-                  "kind": args.kind, "by": args.by, "tile": list(tile), "size": list(size), "budget": args.budget,
-                  "max_per_image": args.max_per_image, "seed": args.seed, "images": M, "total_pixels": total,
-                  "pixels_asked": budget_pixels, "pixels_spent": spent, "spent_share": spent / total,
-                  "tiles": int(M * T), "tiles_selected": len(chosen), "images_touched": len(touched),
-                  "tiles_per_image_mean": len(chosen) / max(1, len(touched)), "tiles_per_image_max": int(per_image_tiles.max()),
-                  "mean_uncertainty_selected": float(U[sel_idx].mean()) if chosen else 0.0,
-                  "mean_uncertainty_all": float(U[live].mean()) if bool(live.any()) else 0.0,
-                  "mean_impurity_selected": float(I[sel_idx].mean()) if chosen else 0.0,
-                  "mean_impurity_all": float(I[live].mean()) if bool(live.any()) else 0.0,
-                  "predicted_selected": hist_sel.tolist(), "predicted_all": hist_all.tolist(),
-                  "nonfinite": int(head_counters["nonfinite"].item()), "previous": args.previous}
-        if labelled:
-            recall = {}
-            for by in CRITERIA:
-                recall[by] = error_recall(table, torch.tensor(choose(by)[1], dtype=torch.long))
-            report.update(error_recall=recall, error_recall_chosen=error_recall(table, sel_idx),
-                          wrong_pixels=int(table[:, 2].sum()), valid_pixels=int(table[:, 3].sum()))
-
-        # ---- pass 2: only images with a selected tile (every image where an earlier round or fill labels come in)
-        labels_dir = names = images_dir = None
-        if args.out_root:
-            labels_dir, names, images_dir = plan_label_tree(args)
-            if len(names) != M:
-                raise RuntimeError(f"--out-root: {len(names)} label names for {M} images")
-        if args.out:
-            os.makedirs(args.out, exist_ok=True)
-        everywhere = bool(args.previous_root or args.fill_root)
-        counters = new_apply_counters(nc, dev, APPLY_COUNTERS if labelled else ("shown", "kept", "filled"))
-        written = []
+        table, stems, given, nonfinite = _table_pass(args, head, tile, pool)
+        sp = _split(args, table, stems, tile, head.size)
+        scores, chosen, spent = _choose(args, table, sp, args.by, head.labelled)
+        report, selection, touched = _report(args, head, table, stems, sp, tile, scores, chosen, spent, nonfinite)
         if args.out or args.out_root:
-            map_png, tree_png, image_png = hc.PngWriter(pool, args.out), hc.PngWriter(pool, labels_dir), \
-                hc.PngWriter(pool, images_dir)
-            empty = np.full(size, 255, dtype=np.uint8)
-            i0 = 0
-            for s, images, target in rc.image_or_dataset_batches(args, nc, pool, dev, unique_stems=True):
-                n = len(s)
-                idx = [j for j in range(n) if everywhere or (i0 + j) in set(touched)]
-                for png in (map_png, tree_png, image_png):
-                    png.wait()                             # the batch before this one: bounds what is in flight
-                if idx:
-                    pick = torch.tensor(idx, dtype=torch.long, device=dev)
-                    sel = selected[[i0 + j for j in idx]].contiguous().to(dev)
-                    prev = fill = None
-                    if args.previous_root:
-                        prev = _read_labels(args.previous_root, args.layout, args.subset, [names[i0 + j] for j in idx], size,
-                                            "--previous-root").to(dev)
-                    if args.fill_root:
-                        fill = _read_labels(args.fill_root, args.layout, args.subset, [names[i0 + j] for j in idx], size,
-                                            "--fill-root").to(dev)
-                    tgt = target[pick].contiguous() if target is not None else None
-                    out, mask = acquire_apply(sel, size, tile, nc, tgt, prev, fill, ignore if labelled else -1, 255, counters,
-                                              want_out=bool(args.out_root), want_mask=bool(args.out))
-                    if args.out:
-                        _, qmap = acquire_head(features(images[pick].contiguous()), w, b, tile, args.kind, want_qmap=True)
-                        unc = (q_values(qmap) >> 8).to(torch.uint8).cpu().numpy()
-                        host = mask.cpu().numpy()
-                        for k, j in enumerate(idx):
-                            map_png.submit(host[k], f"{s[j]}_select.png")
-                            map_png.submit(unc[k], f"{s[j]}_uncertainty.png")
-                    if args.out_root:
-                        out = torch.where(out == ignore, torch.full_like(out, 255), out)   # the label files' own ignore value
-                        host = out.cpu().numpy()
-                        for k, j in enumerate(idx):
-                            tree_png.submit(host[k], names[i0 + j])
-                if args.out_root:
-                    for j in range(n):
-                        if j not in idx:
-                            tree_png.submit(empty, names[i0 + j])
-                    if images_dir:
-                        pics = (images.permute(0, 2, 3, 1) * 255.0).round().clamp(0, 255).to(torch.uint8).cpu().numpy()
-                        for j, stem in enumerate(s):
-                            image_png.submit(pics[j], f"{stem}.png")
-                i0 += n
-            for png in (map_png, tree_png, image_png):
-                png.wait()
-                written.extend(png.written)
-            c = {k: v.cpu() for k, v in counters.items()}
-            report.update(shown=int(c["shown"]), kept=c["kept"].tolist(), filled=c["filled"].tolist())
-            if labelled:
-                if int(c["bad_targets"]):
-                    raise RuntimeError(f"acquire: {int(c['bad_targets'])} target pixels are outside [0, {nc})")
-                ann, giv = c["annotated"].tolist(), given.cpu().tolist()
-                report.update(annotated=ann, annotated_pixels=sum(ann), given=giv,
-                              annotated_share_per_class=[a / g if g else 0.0 for a, g in zip(ann, giv)])
-    for folder in (args.out_root, args.out):
-        if folder:
-            path = os.path.join(folder, "selection.json")
-            hc.write_json(selection, path)
-            written.append(path)
-    report["written"] = written
-    print(f"{report['dataset']} (task {args.task}): {M} images, {len(chosen)} of {M * T} tiles of {tile[0]} x {tile[1]} in "
-          f"{len(touched)} images by {args.by} ({args.kind}): {spent} pixels of {budget_pixels:.0f} asked "
-          f"({spent / total * 100:.2f} % of the split); {report['nonfinite']} non-finite pixels")
+            gained, written = _write_pass(args, head, tile, pool, sp, chosen, touched, given)
+            report.update(gained)
+    print(f"{report['dataset']} (task {args.task}): {sp.M} images, {len(chosen)} of {sp.M * sp.T} tiles of {tile[0]} x {tile[1]} in "
+          f"{len(touched)} images by {args.by} ({args.kind}): {spent} pixels of {sp.budget_pixels:.0f} asked "
+          f"({spent / sp.total * 100:.2f} % of the split); {report['nonfinite']} non-finite pixels")
     print(f"  mean uncertainty {report['mean_uncertainty_selected']:.4f} selected / {report['mean_uncertainty_all']:.4f} all; "
           f"mean impurity {report['mean_impurity_selected']:.4f} / {report['mean_impurity_all']:.4f}")
-    if labelled:
+    if head.labelled:
         print("  error recall at the budget: " + "  ".join(f"{k} {v * 100:.2f} %" for k, v in report["error_recall"].items()))
-    if written:
-        print(f"{len(written)} files written")
-    if args.json:
-        hc.write_json(report, args.json)
-    return report
+    return ac.finish(report, written, args, selection)
 
 
 def _refusals(args):
     """Raise a RuntimeError that names why this combination of flags is refused."""
-    if sum(bool(v) for v in (args.images, args.dataset, args.synthetic)) != 1:
-        raise RuntimeError("give one source of images: --images DIR, --dataset cityscapes|BDD|IDD or --synthetic N")
-    if min(args.height, args.width, args.batch_size) < 1 or args.synthetic < 0:
-        raise RuntimeError("sizes and --batch-size must be positive")
-    if args.height % 2 or args.width % 2:
-        raise RuntimeError("--height and --width must be even")
-    if not (args.json or args.out or args.out_root):
-        raise RuntimeError("nothing to do: give --json FILE, --out DIR or --out-root ROOT")
-    if not 0.0 < args.budget <= 1.0:
-        raise RuntimeError(f"--budget {args.budget} outside (0, 1]: a share of the split's pixels")
+    ac.refuse_head(args, "the split's")
     if args.max_per_image is not None and not 0.0 < args.max_per_image <= 1.0:
         raise RuntimeError(f"--max-per-image {args.max_per_image} outside (0, 1]: a share of one image's pixels")
     check_tile("--tile", args.tile)
-    if args.images and args.by == "oracle":
-        raise RuntimeError("--by oracle needs labels: give --dataset or --synthetic")
-    if args.out_root and args.images:
-        raise RuntimeError("--out-root writes what an annotator would answer: it needs labels (--dataset or --synthetic); "
-                           "with --images give --out DIR")
-    if bool(args.out_root) != bool(args.layout):
-        raise RuntimeError("--out-root and --layout cityscapes|BDD go together")
-    if args.out_root and args.dataset == "IDD":
-        raise RuntimeError("--out-root does not take --dataset IDD: its loaders remap level-3 ids, so the label "
-                           "files would need the inverse map")
-    if (args.previous_root or args.fill_root) and not args.out_root:
-        raise RuntimeError("--previous-root and --fill-root are label trees laid out as --out-root lays its own: they need "
-                           "--out-root and --layout")
-    if args.previous_root and not args.previous:
-        raise RuntimeError("--previous-root goes with --previous SEL.json, the selection that tree was written for")
+    ac.refuse_rounds(args)
 
 
 def build_parser():
     p = hc.RefusingParser(_refusals, description="which regions of a split to label first: tile scores from a fused "
                                                  "head kernel, a ranking under a pixel budget, and the label tree an "
                                                  "annotator of those tiles would hand back")
-    p.add_argument("--state", required=True, help="checkpoint written by the trainers (or by the reference)")
-    p.add_argument("--num-classes", type=int, nargs="+", required=True)
-    p.add_argument("--task", type=int, required=True, help="which task's decoder predicts")
-    p.add_argument("--images", help="folder of unlabelled .jpg / .png images (searched recursively)")
-    rc.add_data_flags(p, dataset_help="a labelled dataset instead: the run simulates the annotator",
-                      synthetic_help="N procedural images instead (labelled)")
-    p.set_defaults(subset="train")
-    p.add_argument("--budget", type=float, required=True, help="share of the split's pixels that may be shown")
+    ac.add_source_flags(p, "share of the split's pixels that may be shown")
     p.add_argument("--tile", type=int, nargs=2, default=[32, 32], metavar=("TH", "TW"),
                    help="tile size in label pixels, each even and in [2, 256] (default %(default)s)")
-    p.add_argument("--kind", choices=KINDS, default="entropy", help="the per-pixel uncertainty (default %(default)s)")
-    p.add_argument("--by", choices=CRITERIA, default="ripu", help="the tile criterion (default %(default)s)")
-    p.add_argument("--seed", type=int, default=0, help="of --by random (default %(default)s)")
+    ac.add_criterion_flags(p, KINDS, CRITERIA, "the tile criterion")
     p.add_argument("--max-per-image", type=float, help="skip a tile once its image has this share of its pixels selected")
-    p.add_argument("--previous", help="an earlier round's selection.json: its tiles leave the ranking")
-    p.add_argument("--previous-root", help="the label tree of that round: its labelled pixels are kept")
-    p.add_argument("--fill-root", help="a label tree (pseudo --out-root, say) for the pixels still empty")
-    p.add_argument("--json", help="write the report here")
-    p.add_argument("--out", help="write <stem>_select.png (255 selected, 128 kept, 64 filled) and <stem>_uncertainty.png "
-                                 "(q >> 8) here")
-    p.add_argument("--out-root", help="with labels: write a dataset tree the trainers open as --cs-datadir / --bdd-datadir")
-    p.add_argument("--layout", choices=("cityscapes", "BDD"), help="the tree --out-root writes")
+    ac.add_round_flags(p, "its tiles leave the ranking", "<stem>_uncertainty.png (q >> 8)")
     return p
 
 

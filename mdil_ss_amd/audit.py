@@ -32,6 +32,7 @@ import os
 
 import torch
 
+from . import _annotate_common as ac
 from . import _audit_lib
 from . import _head_common as hc
 from . import _report_common as rc
@@ -377,43 +378,23 @@ def main(args):
 
     from . import predict as P
     palette = P.default_palette(nc).to(dev) if args.out else None
-    labels_dir = names = images_dir = None
-    if args.clean_root:
-        labels_dir, names, images_dir = plan_clean_tree(args)
-    if args.out:
-        os.makedirs(args.out, exist_ok=True)
     max_q = [max_q_of(args.max_self_confidence)] * nc
     acted = new_apply_counters(nc, dev)
-    stems, written = [], []
+    stems = []
     with hc.png_pool() as pool:
-        issue_png, clean_png = hc.PngWriter(pool, args.out), hc.PngWriter(pool, labels_dir)
-        image_png = hc.PngWriter(pool, images_dir)
+        writer = ac.LabelTreeWriter(pool, args, "--clean-root", args.clean_root, args.out)
         for s, images, target in rc.batches(args, nc, dev, unique_stems=bool(args.out)):
             selfq, suggest = meter.audit(model, images, args.task, target=target)
-            if args.out or args.clean_root:
-                out, mask = audit_apply(target, suggest, selfq, nc, max_q, args.mode, ignore, 255, 255, acted,
-                                        want_out=bool(args.clean_root), want_mask=True)
-                for png in (issue_png, clean_png, image_png):
-                    png.wait()                         # the batch before this one: bounds what is in flight
+            writer.wait()
+            out, mask = audit_apply(target, suggest, selfq, nc, max_q, args.mode, ignore, 255, 255, acted, want_mask=True,
+                                    want_out=bool(args.clean_root)) if args.out or args.clean_root else (None, None)
             if args.out:
                 grey = torch.full((1, 3), GREY, dtype=torch.uint8, device=dev)
                 colour = torch.where((mask != 0).unsqueeze(3), palette[suggest.long().clamp(max=nc - 1)], grey)
-                host = colour.cpu().numpy()
-                for j, stem in enumerate(s):
-                    issue_png.submit(host[j], f"{stem}_issues.png")
-            if args.clean_root:
-                out = torch.where(out == ignore, torch.full_like(out, 255), out)   # the label files' own ignore value
-                host = out.cpu().numpy()
-                for j in range(host.shape[0]):
-                    clean_png.submit(host[j], names[len(stems) + j])
-                if images_dir:
-                    pics = (images.permute(0, 2, 3, 1) * 255.0).round().clamp(0, 255).to(torch.uint8).cpu().numpy()
-                    for j, stem in enumerate(s):
-                        image_png.submit(pics[j], f"{stem}.png")
+                writer.write_maps(s, issues=colour)
+            writer.write_batch(s, images, out, ignore)
             stems.extend(s)
-        for png in (issue_png, clean_png, image_png):
-            png.wait()
-            written.extend(png.written)
+        written = writer.close()
     c = meter.counters()
     joint, count = c["joint"], c["count"]
     report.update(images=len(stems), labelled_pixels=int(count.sum()), count=count.tolist(),
@@ -429,11 +410,7 @@ def main(args):
     for pair in report["top_pairs"][:5]:
         print(f"  given {pair['given']:2d} -> suggested {pair['suggested']:2d}: {pair['joint'] * 100:.3f} % of the labels "
               f"({pair['confident_pixels']} confident pixels)")
-    if written:
-        print(f"{len(written)} files written")
-    if args.json:
-        hc.write_json(report, args.json)
-    return report
+    return ac.finish(report, written, args)
 
 
 def _refusals(args):
@@ -443,11 +420,7 @@ def _refusals(args):
         raise RuntimeError("nothing to do: give --json FILE, --fit FILE, --out DIR or --clean-root ROOT")
     if args.fit and args.thresholds:
         raise RuntimeError("--fit FILE writes the thresholds of this split, --thresholds FILE reads saved ones: give one")
-    if bool(args.clean_root) != bool(args.layout):
-        raise RuntimeError("--clean-root and --layout cityscapes|BDD go together")
-    if args.clean_root and args.dataset == "IDD":
-        raise RuntimeError("--clean-root does not take --dataset IDD: its loaders remap level-3 ids, so the label "
-                           "files would need the inverse map")
+    ac.refuse_tree(args, "--clean-root", args.clean_root)
     if not 0.0 <= args.max_self_confidence <= 1.0:
         raise RuntimeError(f"--max-self-confidence {args.max_self_confidence} outside [0, 1]")
     if args.top < 0:

@@ -58,7 +58,6 @@ constexpr int kLabelRounds = 4;                      // ballot rounds over label
 constexpr int kFlushEvery = 31;                      // trips between two flushes of the LDS table
 constexpr int kMapWG = 256;
 constexpr int kMapMaxBlocks = 512;                   // beyond 131,072 items (of 8 pixels) the loop strides
-constexpr int kApplyFlushEvery = 1 << 19;            // trips; a trip adds at most 2048 counts per work-group
 constexpr char kFnHead[] = "acquire_head";
 constexpr char kFnApply[] = "acquire_apply";
 
@@ -291,10 +290,8 @@ __global__ __launch_bounds__(kMapWG) void acquire_apply_kernel(
     unsigned char* __restrict__ mask, u64* __restrict__ shown, u64* __restrict__ annotated, u64* __restrict__ kept,
     u64* __restrict__ filled, u64* __restrict__ bad_targets) {
   __shared__ uint32_t Al[kMaxC], Kl[kMaxC], Fl[kMaxC];               // annotated, kept, filled
-  __shared__ uint32_t shown_l, bad_t;
-  for (int c = threadIdx.x; c < nc; c += kMapWG) Al[c] = Kl[c] = Fl[c] = 0u;
-  if (threadIdx.x == 0) shown_l = bad_t = 0u;
-  __syncthreads();
+  __shared__ uint32_t misc[2];                                       // shown, bad targets
+  zero_annotator<kMapWG>(Al, Kl, Fl, nc, misc);
 
   const long long HWl = (long long)Hl * Wl;
   int trips = 0;
@@ -322,27 +319,8 @@ __global__ __launch_bounds__(kMapWG) void acquire_apply_kernel(
         ob[j] = (uint32_t)drop_id;
         mb[j] = 0u;
         if (j < n) {
-          if (sel) {
-            ++nshown;
-            mb[j] = 255u;
-            if (target) {
-              ob[j] = tg[j];
-              if ((int)tg[j] != ignore_index) {
-                if (tg[j] < (uint32_t)nc)
-                  ann_run.add((int)tg[j]);
-                else
-                  ++nbad;
-              }
-            }
-          } else if (previous && pv[j] != (uint32_t)drop_id) {
-            ob[j] = pv[j];
-            mb[j] = 128u;
-            if (pv[j] < (uint32_t)nc) kept_run.add((int)pv[j]);
-          } else if (fill && fl[j] != (uint32_t)drop_id) {
-            ob[j] = fl[j];
-            mb[j] = 64u;
-            if (fl[j] < (uint32_t)nc) fill_run.add((int)fl[j]);
-          }
+          annotate_pixel(sel, target, tg[j], previous, pv[j], fill, fl[j], nc, ignore_index, drop_id, ann_run, kept_run,
+                         fill_run, ob[j], mb[j], nshown, nbad);
           // the next pixel of the flat map
           if (j + 1 < n) {
             bool moved = false;
@@ -372,8 +350,8 @@ __global__ __launch_bounds__(kMapWG) void acquire_apply_kernel(
       ann_run.done();
       kept_run.done();
       fill_run.done();
-      if (nshown) atomicAdd(&shown_l, nshown);
-      if (nbad) atomicAdd(&bad_t, nbad);
+      if (nshown) atomicAdd(&misc[0], nshown);
+      if (nbad) atomicAdd(&misc[1], nbad);
       if (out) store_bytes(out, o, n, ob);
       if (mask) store_bytes(mask, o, n, mb);
     }
@@ -381,16 +359,8 @@ __global__ __launch_bounds__(kMapWG) void acquire_apply_kernel(
     const bool last = base + (long long)gridDim.x * kMapWG >= nitems;
     if (last || ++trips == kApplyFlushEvery) {                     // uniform over the work-group
       trips = 0;
-      __syncthreads();
-      flush_counters<kMapWG>(Al, nc, annotated);
-      flush_counters<kMapWG>(Kl, nc, kept);
-      flush_counters<kMapWG>(Fl, nc, filled);
-      if (threadIdx.x == 0) {
-        if (shown_l && shown) __hip_atomic_fetch_add(shown, (u64)shown_l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (bad_t && bad_targets) __hip_atomic_fetch_add(bad_targets, (u64)bad_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        shown_l = bad_t = 0u;
-      }
-      __syncthreads();
+      u64* const dst[2] = {shown, bad_targets};
+      flush_annotator<kMapWG>(Al, Kl, Fl, nc, annotated, kept, filled, misc, dst);
     }
   }
 }
@@ -475,24 +445,12 @@ API int mdil_acquire_apply(const unsigned char* selected, const unsigned char* t
   if (!classes_ok(kFnApply, nc, MDIL_ACQUIRE_MIN_CLASSES, MDIL_ACQUIRE_MAX_CLASSES)) return MDIL_ACQUIRE_ERR_INVALID;
   if (!tile_ok(kFnApply, th, tw)) return MDIL_ACQUIRE_ERR_INVALID;
   if (!ignore_ok(kFnApply, ignore_index)) return MDIL_ACQUIRE_ERR_INVALID;
-  if (drop_id < 0 || drop_id > 255) {
-    set_error("acquire_apply: drop_id=%d outside [0, 255]", drop_id);
+  if (!byte_id_ok(kFnApply, "drop_id", drop_id)) return MDIL_ACQUIRE_ERR_INVALID;
+  if (!apply_outputs_ok(kFnApply, {out, mask, shown, annotated, kept, filled, bad_targets})) return MDIL_ACQUIRE_ERR_INVALID;
+  if (!apply_target_ok(kFnApply, target, annotated, bad_targets)) return MDIL_ACQUIRE_ERR_INVALID;
+  if (!aligned8_ok(kFnApply, "target, previous, fill, out, mask and the counters",
+                   {target, previous, fill, out, mask, shown, annotated, kept, filled, bad_targets}))
     return MDIL_ACQUIRE_ERR_INVALID;
-  }
-  if (!out && !mask && !shown && !annotated && !kept && !filled && !bad_targets) {
-    set_error("acquire_apply: nothing to write (out, mask and every counter are NULL)");
-    return MDIL_ACQUIRE_ERR_INVALID;
-  }
-  if (!target && (annotated || bad_targets)) {
-    set_error("acquire_apply: annotated and bad_targets need a target");
-    return MDIL_ACQUIRE_ERR_INVALID;
-  }
-  if (((uintptr_t)target & 7) || ((uintptr_t)previous & 7) || ((uintptr_t)fill & 7) || ((uintptr_t)out & 7) ||
-      ((uintptr_t)mask & 7) || ((uintptr_t)shown & 7) || ((uintptr_t)annotated & 7) || ((uintptr_t)kept & 7) ||
-      ((uintptr_t)filled & 7) || ((uintptr_t)bad_targets & 7)) {
-    set_error("acquire_apply: alignment (target, previous, fill, out, mask and the counters 8 B)");
-    return MDIL_ACQUIRE_ERR_INVALID;
-  }
   const long long npix = (long long)N * Hl * Wl;
   const long long nitems = (npix + kPerItem - 1) / kPerItem;
   const int Ty = (Hl + th - 1) / th, Tx = (Wl + tw - 1) / tw;

@@ -14,13 +14,15 @@
 //   pseudo          vote, stage_head, logits4, ignore_ok
 //   openset         vote
 //   audit           vote, shape_ok, ignore_ok
-//   acquire         vote, shape_ok, ignore_ok
+//   acquire         vote, shape_ok, ignore_ok, byte_id_ok, apply_outputs_ok, apply_target_ok, aligned8_ok
+//   ripu            ignore_ok, byte_id_ok, apply_outputs_ok, apply_target_ok, aligned8_ok (no device code of this header)
 // pseudo, openset, audit, acquire and route share more through map_common.h, which includes this header: the
 // per-parity Wp staging and chain, the LDS tables of integer adds and the helpers of the map kernels.
 // calib_head.hip forms its logits per parity from its own Wp[a*2+b][c][ci] staging, not through
 // logits4 (another LDS layout, the same chain), and keeps its DPP sums.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -210,6 +212,35 @@ inline bool colour_ok(const char* fn, const void* colour, const void* palette) {
 inline bool ignore_ok(const char* fn, int ignore_index) {
   if (ignore_index >= -1 && ignore_index <= 255) return true;
   set_error("%s: ignore_index=%d outside [-1, 255]", fn, ignore_index);
+  return false;
+}
+
+// The annotator's entry points (acquire_apply, ripu_apply): an id that is a byte; at least one output; the
+// counters that need a target; every pointer of `ptrs` (`what` names them) on an 8-byte boundary.
+inline bool byte_id_ok(const char* fn, const char* name, int id) {
+  if (id >= 0 && id <= 255) return true;
+  set_error("%s: %s=%d outside [0, 255]", fn, name, id);
+  return false;
+}
+
+inline bool apply_outputs_ok(const char* fn, std::initializer_list<const void*> outputs) {
+  for (const void* p : outputs)
+    if (p) return true;
+  set_error("%s: nothing to write (out, mask and every counter are NULL)", fn);
+  return false;
+}
+
+inline bool apply_target_ok(const char* fn, const void* target, const void* annotated, const void* bad_targets) {
+  if (target || (!annotated && !bad_targets)) return true;
+  set_error("%s: annotated and bad_targets need a target", fn);
+  return false;
+}
+
+inline bool aligned8_ok(const char* fn, const char* what, std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= (uintptr_t)p;
+  if (!(bits & 7)) return true;
+  set_error("%s: alignment (%s 8 B)", fn, what);
   return false;
 }
 

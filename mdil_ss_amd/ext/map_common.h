@@ -1,7 +1,7 @@
 // What the map add-ons share beyond head_common.h, written once: pseudo, openset, audit and acquire (a head
-// kernel that counts into integer tables, then kernels over the stored 8- and 16-bit maps) and route, whose
-// head kernel walks the same per-parity chain.  Private to mdil_ss_amd/ext like head_common.h and compiled INTO
-// each of the five libraries, which stay self-contained binaries.  It is a header of its own because
+// kernel that counts into integer tables, then kernels over the stored 8- and 16-bit maps), route, whose head
+// kernel walks the same per-parity chain, and ripu, whose kernels read stored maps alone.  Private to
+// mdil_ss_amd/ext like head_common.h and compiled INTO each of the six libraries, which stay self-contained binaries.  It is a header of its own because
 // head_common.h's device code is also compiled into predict / fullres / ensemble / drift / calib, whose
 // bytes are not to move.  The arithmetic contracts (order of operations, roundings) are documented in the
 // kernels' header comments; the helpers here are the single spelling of the steps they name.  Who uses what:
@@ -10,10 +10,12 @@
 //              load_bytes, store_bytes, flush_counters
 //   audit      u64, kLog2e, is_finite, wave_sum_u32, quad_bytes, Run, load_bytes, store_bytes, flush_counters
 //   acquire    u64, kLog2e, is_finite, wave_sum_u32, quad_bytes, cached_add, flush_cache, Run, load_bytes,
-//              store_bytes, flush_counters
+//              store_bytes, flush_counters, kApplyFlushEvery, annotate_pixel, zero_annotator, flush_annotator
 //              (audit_head and acquire_head keep stage_parity and parity_logits spelled out: as calls they cost
 //              0.5 to 1.5 % of those kernels' time, past the measured margin; see the comments at the call sites)
 //   route      kLog2e, is_finite, stage_parity, parity_logits
+//   ripu       u64, Run, load_bytes, store_bytes, flush_counters, kApplyFlushEvery, annotate_pixel, zero_annotator,
+//              flush_annotator (no head code)
 // What differs on purpose stays in its file, where a comment says why: the three quantise rules and code16, each
 // file's wave_merged_add(s), route's fold_rows, pseudo_head's logits4 chain and its load_item.
 #pragma once
@@ -170,6 +172,71 @@ __device__ __forceinline__ void store_bytes(unsigned char* __restrict__ map, lon
     for (int j = 0; j < kPerItem; ++j)
       if (j < n) map[o + j] = (unsigned char)v[j];
   }
+}
+
+// ------------------------------------------------------------------------- the annotator's rule
+// What acquire_apply and ripu_apply do with one pixel, and how their work-groups count.  They differ in where `sel`
+// comes from (a tile look-up that steps along the row; a byte that equals 255) and in ripu's two wrong counts, which
+// stay in their files.
+constexpr int kApplyFlushEvery = 1 << 19;            // trips; a trip adds at most 2048 counts per work-group
+
+// One pixel, whose ob and mb come in as drop_id and 0: selected -> the target (where there is one), 255 in the mask;
+// else `previous` where that is not drop_id -> kept, 128; else `fill` where that is not drop_id -> filled, 64.  A
+// NULL map is absent and its byte (tg, pv, fl) is not read.  The three runs count the classes below nc; nshown counts the selected
+// pixels, nbad the selected targets that are neither a class nor ignore_index.
+__device__ __forceinline__ void annotate_pixel(bool sel, const unsigned char* target, const uint32_t& tg,
+                                               const unsigned char* previous, const uint32_t& pv,
+                                               const unsigned char* fill, const uint32_t& fl, int nc, int ignore_index,
+                                               int drop_id, Run& ann_run, Run& kept_run, Run& fill_run, uint32_t& ob,
+                                               uint32_t& mb, uint32_t& nshown, uint32_t& nbad) {
+  if (sel) {
+    ++nshown;
+    mb = 255u;
+    if (target) {
+      ob = tg;
+      if ((int)tg != ignore_index) {
+        if (tg < (uint32_t)nc)
+          ann_run.add((int)tg);
+        else
+          ++nbad;
+      }
+    }
+  } else if (previous && pv != (uint32_t)drop_id) {
+    ob = pv;
+    mb = 128u;
+    if (pv < (uint32_t)nc) kept_run.add((int)pv);
+  } else if (fill && fl != (uint32_t)drop_id) {
+    ob = fl;
+    mb = 64u;
+    if (fl < (uint32_t)nc) fill_run.add((int)fl);
+  }
+}
+
+// The work-group's LDS counters before its first item: Al / Kl / Fl (annotated, kept, filled per class) and the K
+// scalar ones.  The barrier is inside.
+template <int WG, int K>
+__device__ __forceinline__ void zero_annotator(uint32_t* Al, uint32_t* Kl, uint32_t* Fl, int nc, uint32_t (&misc)[K]) {
+  for (int c = threadIdx.x; c < nc; c += WG) Al[c] = Kl[c] = Fl[c] = 0u;
+  if (threadIdx.x < K) misc[threadIdx.x] = 0u;
+  __syncthreads();
+}
+
+// Those counters -> global memory (NULL destinations only clear), and they are zero again; called where the whole
+// work-group arrives: after its last trip and every kApplyFlushEvery trips.  The barriers are inside.
+template <int WG, int K>
+__device__ __forceinline__ void flush_annotator(uint32_t* Al, uint32_t* Kl, uint32_t* Fl, int nc, u64* annotated,
+                                                u64* kept, u64* filled, uint32_t (&misc)[K], u64* const (&dst)[K]) {
+  __syncthreads();
+  flush_counters<WG>(Al, nc, annotated);
+  flush_counters<WG>(Kl, nc, kept);
+  flush_counters<WG>(Fl, nc, filled);
+  if (threadIdx.x < K) {
+    const uint32_t v = misc[threadIdx.x];
+    if (v && dst[threadIdx.x])
+      __hip_atomic_fetch_add(dst[threadIdx.x], (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    misc[threadIdx.x] = 0u;
+  }
+  __syncthreads();
 }
 
 }  // namespace

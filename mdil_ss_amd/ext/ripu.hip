@@ -55,7 +55,6 @@ constexpr int kMaxChunks = 4096;                      // 32 KB of 64-bit words
 constexpr int kMinChunkShift = 6;
 constexpr int kMapWG = 256;
 constexpr int kMapMaxBlocks = 512;                    // beyond 131,072 items (of 8 pixels) the loop strides
-constexpr int kApplyFlushEvery = 1 << 19;             // trips; a trip adds at most 2048 counts per work-group
 constexpr char kFnScore[] = "ripu_score";
 constexpr char kFnSelect[] = "ripu_select";
 constexpr char kFnApply[] = "ripu_apply";
@@ -328,9 +327,7 @@ __global__ __launch_bounds__(kMapWG) void ripu_apply_kernel(
     u64* __restrict__ wrong_all) {
   __shared__ uint32_t Al[kMaxC], Kl[kMaxC], Fl[kMaxC];               // annotated, kept, filled
   __shared__ uint32_t misc[4];                                       // shown, bad targets, wrong shown, wrong all
-  for (int c = threadIdx.x; c < nc; c += kMapWG) Al[c] = Kl[c] = Fl[c] = 0u;
-  if (threadIdx.x < 4) misc[threadIdx.x] = 0u;
-  __syncthreads();
+  zero_annotator<kMapWG>(Al, Kl, Fl, nc, misc);
 
   const bool judge = target && label;
   int trips = 0;
@@ -356,28 +353,9 @@ __global__ __launch_bounds__(kMapWG) void ripu_apply_kernel(
           const bool sel = sl[j] == 255u;
           const bool wrong = judge && tg[j] < (uint32_t)nc && (int)tg[j] != ignore_index && lb[j] != tg[j];
           nwa += wrong ? 1u : 0u;
-          if (sel) {
-            ++nshown;
-            nws += wrong ? 1u : 0u;
-            mb[j] = 255u;
-            if (target) {
-              ob[j] = tg[j];
-              if ((int)tg[j] != ignore_index) {
-                if (tg[j] < (uint32_t)nc)
-                  ann_run.add((int)tg[j]);
-                else
-                  ++nbad;
-              }
-            }
-          } else if (previous && pv[j] != (uint32_t)drop_id) {
-            ob[j] = pv[j];
-            mb[j] = 128u;
-            if (pv[j] < (uint32_t)nc) kept_run.add((int)pv[j]);
-          } else if (fill && fl[j] != (uint32_t)drop_id) {
-            ob[j] = fl[j];
-            mb[j] = 64u;
-            if (fl[j] < (uint32_t)nc) fill_run.add((int)fl[j]);
-          }
+          if (sel && wrong) ++nws;
+          annotate_pixel(sel, target, tg[j], previous, pv[j], fill, fl[j], nc, ignore_index, drop_id, ann_run, kept_run,
+                         fill_run, ob[j], mb[j], nshown, nbad);
         }
       }
       ann_run.done();
@@ -394,18 +372,8 @@ __global__ __launch_bounds__(kMapWG) void ripu_apply_kernel(
     const bool last = base + (long long)gridDim.x * kMapWG >= nitems;
     if (last || ++trips == kApplyFlushEvery) {                       // uniform over the work-group
       trips = 0;
-      __syncthreads();
-      flush_counters<kMapWG>(Al, nc, annotated);
-      flush_counters<kMapWG>(Kl, nc, kept);
-      flush_counters<kMapWG>(Fl, nc, filled);
-      if (threadIdx.x < 4) {
-        u64* dst[4] = {shown, bad_targets, wrong_shown, wrong_all};
-        const uint32_t v = misc[threadIdx.x];
-        if (v && dst[threadIdx.x])
-          __hip_atomic_fetch_add(dst[threadIdx.x], (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        misc[threadIdx.x] = 0u;
-      }
-      __syncthreads();
+      u64* const dst[4] = {shown, bad_targets, wrong_shown, wrong_all};
+      flush_annotator<kMapWG>(Al, Kl, Fl, nc, annotated, kept, filled, misc, dst);
     }
   }
 }
@@ -533,29 +501,18 @@ API int mdil_ripu_apply(const unsigned char* selected, const unsigned char* targ
   if (!maps_ok(kFnApply, N, Hl, Wl)) return MDIL_RIPU_ERR_INVALID;
   if (!classes_ok(kFnApply, nc, MDIL_RIPU_MIN_CLASSES, MDIL_RIPU_MAX_CLASSES)) return MDIL_RIPU_ERR_INVALID;
   if (!ignore_ok(kFnApply, ignore_index)) return MDIL_RIPU_ERR_INVALID;
-  if (drop_id < 0 || drop_id > 255) {
-    set_error("ripu_apply: drop_id=%d outside [0, 255]", drop_id);
+  if (!byte_id_ok(kFnApply, "drop_id", drop_id)) return MDIL_RIPU_ERR_INVALID;
+  if (!apply_outputs_ok(kFnApply, {out, mask, shown, annotated, kept, filled, bad_targets, wrong_shown, wrong_all}))
     return MDIL_RIPU_ERR_INVALID;
-  }
-  if (!out && !mask && !shown && !annotated && !kept && !filled && !bad_targets && !wrong_shown && !wrong_all) {
-    set_error("ripu_apply: nothing to write (out, mask and every counter are NULL)");
-    return MDIL_RIPU_ERR_INVALID;
-  }
-  if (!target && (annotated || bad_targets)) {
-    set_error("ripu_apply: annotated and bad_targets need a target");
-    return MDIL_RIPU_ERR_INVALID;
-  }
+  if (!apply_target_ok(kFnApply, target, annotated, bad_targets)) return MDIL_RIPU_ERR_INVALID;
   if ((!target || !label) && (wrong_shown || wrong_all)) {
     set_error("ripu_apply: wrong_shown and wrong_all need a target and a label map");
     return MDIL_RIPU_ERR_INVALID;
   }
-  if (((uintptr_t)selected & 7) || ((uintptr_t)target & 7) || ((uintptr_t)previous & 7) || ((uintptr_t)fill & 7) ||
-      ((uintptr_t)label & 7) || ((uintptr_t)out & 7) || ((uintptr_t)mask & 7) || ((uintptr_t)shown & 7) ||
-      ((uintptr_t)annotated & 7) || ((uintptr_t)kept & 7) || ((uintptr_t)filled & 7) || ((uintptr_t)bad_targets & 7) ||
-      ((uintptr_t)wrong_shown & 7) || ((uintptr_t)wrong_all & 7)) {
-    set_error("ripu_apply: alignment (selected, target, previous, fill, label, out, mask and the counters 8 B)");
+  if (!aligned8_ok(kFnApply, "selected, target, previous, fill, label, out, mask and the counters",
+                   {selected, target, previous, fill, label, out, mask, shown, annotated, kept, filled, bad_targets,
+                    wrong_shown, wrong_all}))
     return MDIL_RIPU_ERR_INVALID;
-  }
   const long long npix = (long long)N * Hl * Wl;
   const long long nitems = (npix + kPerItem - 1) / kPerItem;
   const int grid = bounded_grid(nitems, kMapWG, kMapMaxBlocks);

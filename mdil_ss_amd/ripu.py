@@ -34,11 +34,12 @@ measured on a randomly initialised network only: nothing says which criterion fi
 head on BDD or IDD.  No retraining on the selected labels is run."""
 import json
 import math
-import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+from . import _annotate_common as ac
 from . import _head_common as hc
 from . import _report_common as rc
 from . import _ripu_lib
@@ -88,8 +89,7 @@ def key_values(key):
 
 
 def apply_counter_shapes(nc):
-    return {"shown": (1,), "annotated": (nc,), "kept": (nc,), "filled": (nc,), "bad_targets": (1,), "wrong_shown": (1,),
-            "wrong_all": (1,)}
+    return dict(A.apply_counter_shapes(nc), wrong_shown=(1,), wrong_all=(1,))
 
 
 def new_apply_counters(nc, dev, names=APPLY_COUNTERS):
@@ -241,116 +241,52 @@ def earlier_marks(stems, before, radius, size):
     return torch.from_numpy(marks)
 
 
-def main(args):
-    _refusals(args)
-    rc.refuse_task(args.task, args.num_classes)
-    if args.previous and not os.path.isfile(args.previous):
-        raise RuntimeError(f"--previous {args.previous}: no such file")
-    for flag, path in (("--previous-root", args.previous_root), ("--fill-root", args.fill_root)):
-        if path and not os.path.isdir(path):
-            raise RuntimeError(f"{flag} {path}: no such folder")
-    dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
-    ignore = nc - 1                                    # the trainers' relabelled ignore class
-    size = (args.height, args.width)
-    labelled = not args.images
-    k = args.radius
-    r = k if args.select_radius is None else args.select_radius
-    budget_pixels = int(math.floor(args.budget * size[0] * size[1]))
-    w, b = (t.detach() for t in model.head_params(args.task))
-    before, before_radius = read_selection(args.previous, size) if args.previous else ({}, 0)
-    others = [by for by in CRITERIA if by != args.by] if labelled else []
-    nonfinite = torch.zeros(1, dtype=torch.int64, device=dev)
-    counters = new_apply_counters(nc, dev, APPLY_COUNTERS if labelled else ("shown", "kept", "filled"))
-    side = {by: new_apply_counters(nc, dev, ("shown", "wrong_shown", "wrong_all")) for by in others}
-    tallies = {by: {"picks": 0, "picks_max": 0, "stops": dict.fromkeys(STOPS, 0)} for by in [args.by] + others}
-    given = torch.zeros(nc, dtype=torch.int64, device=dev)
+def _batch(args, head, run, writer, stems, images, target):
+    """One batch: ``acquire_head``'s maps, score and select by every criterion (the others counted and thrown
+    away), ``ripu_apply`` for the chosen one, the maps of ``--out`` and the tree of ``--out-root``."""
+    nc, size, dev, k, r = head.nc, head.size, head.dev, run.k, run.r
+    label, qmap = A.acquire_head(ac.features(head, images), head.w, head.b, (2, 2), args.kind,
+                                 counters={"nonfinite": run.nonfinite}, want_label=True, want_qmap=True)
+    marks = earlier_marks(stems, run.before, run.before_radius, size).to(dev)
 
-    def tally(by, got):
-        t = tallies[by]
-        count, stop = got["count"].cpu(), got["stop"].cpu()
+    def pick(by):
+        taken = marks.clone()
+        key = ripu_score(label, k, nc, by, qmap, target, head.ign, taken, seed=args.seed, image0=writer.seen)
+        got = ripu_select(key, taken, r, run.budget_pixels, args.max_picks)
+        t = run.tallies[by]
+        count = got["count"].cpu()
         t["picks"] += int(count.sum())
         t["picks_max"] = max(t["picks_max"], int(count.max()))
-        for s in stop.tolist():
+        for s in got["stop"].cpu().tolist():
             t["stops"][STOPS[s]] += 1
+        return key, taken, got
 
-    labels_dir = names = images_dir = None
-    if args.out_root:
-        labels_dir, names, images_dir = A.plan_label_tree(args)
+    for by in run.others:                              # the same score and select, counted and thrown away
+        ripu_apply(pick(by)[1], nc, target, label=label, ignore_index=head.ign, counters=run.side[by], want_out=False)
+    key, taken, got = pick(args.by)
+    prev, fill = writer.earlier_labels(args, range(len(stems)), size, dev)
+    out, mask = ripu_apply(taken, nc, target, prev, fill, label if head.labelled else None, head.ign, 255, run.counters,
+                           want_out=bool(args.out_root), want_mask=bool(args.out))
+    count, picks = got["count"].cpu().tolist(), got["picks"].cpu()
+    for j, stem in enumerate(stems):
+        run.per_stem[stem] = picks[j, :count[j]].tolist()
+    ac.given_counts(run.given, target, nc, head.ignore)
+    writer.wait()
     if args.out:
-        os.makedirs(args.out, exist_ok=True)
-    per_stem, written, stems_all, i0 = {}, [], [], 0
-    with hc.png_pool() as pool:
-        map_png, tree_png, image_png = hc.PngWriter(pool, args.out), hc.PngWriter(pool, labels_dir), \
-            hc.PngWriter(pool, images_dir)
-        for stems, images, target in rc.image_or_dataset_batches(args, nc, pool, dev, unique_stems=True):
-            if tuple(images.shape[2:]) != size:
-                raise RuntimeError(f"images of {tuple(images.shape[2:])}, expected {size}")
-            n = len(stems)
-            with torch.no_grad():
-                feat = model.features(images, args.task).contiguous()
-            label, qmap = A.acquire_head(feat, w, b, (2, 2), args.kind, counters={"nonfinite": nonfinite}, want_label=True,
-                                         want_qmap=True)
-            marks = earlier_marks(stems, before, before_radius, size).to(dev)
-            ign = ignore if labelled else -1
+        writer.write_maps(stems, select=mask, score=(key_values(key) >> 24).to(torch.uint8))
+    writer.write_batch(stems, images, out, head.ignore)
 
-            def run(by, taken):
-                key = ripu_score(label, k, nc, by, qmap, target, ign, taken, seed=args.seed, image0=i0)
-                return key, ripu_select(key, taken, r, budget_pixels, args.max_picks)
 
-            for by in others:                              # the same score and select, counted and thrown away
-                taken = marks.clone()
-                tally(by, run(by, taken)[1])
-                ripu_apply(taken, nc, target, label=label, ignore_index=ign, counters=side[by], want_out=False)
-            taken = marks.clone()
-            key, got = run(args.by, taken)
-            tally(args.by, got)
-            prev = fill = None
-            if args.previous_root:
-                prev = A._read_labels(args.previous_root, args.layout, args.subset, names[i0:i0 + n], size,
-                                      "--previous-root").to(dev)
-            if args.fill_root:
-                fill = A._read_labels(args.fill_root, args.layout, args.subset, names[i0:i0 + n], size, "--fill-root").to(dev)
-            out, mask = ripu_apply(taken, nc, target, prev, fill, label if labelled else None, ign, 255, counters,
-                                   want_out=bool(args.out_root), want_mask=bool(args.out))
-            count, picks = got["count"].cpu().tolist(), got["picks"].cpu()
-            for j, stem in enumerate(stems):
-                per_stem[stem] = picks[j, :count[j]].tolist()
-            if target is not None:
-                tl = target.reshape(-1).long()
-                given += torch.bincount(tl[(tl < nc) & (tl != ignore)], minlength=nc)
-            for png in (map_png, tree_png, image_png):
-                png.wait()                                 # the batch before this one: bounds what is in flight
-            if args.out:
-                score = (key_values(key) >> 24).to(torch.uint8).cpu().numpy()
-                host = mask.cpu().numpy()
-                for j, stem in enumerate(stems):
-                    map_png.submit(host[j], f"{stem}_select.png")
-                    map_png.submit(score[j], f"{stem}_score.png")
-            if args.out_root:
-                out = torch.where(out == ignore, torch.full_like(out, 255), out)   # the label files' own ignore value
-                host = out.cpu().numpy()
-                for j in range(n):
-                    tree_png.submit(host[j], names[i0 + j])
-                if images_dir:
-                    pics = (images.permute(0, 2, 3, 1) * 255.0).round().clamp(0, 255).to(torch.uint8).cpu().numpy()
-                    for j, stem in enumerate(stems):
-                        image_png.submit(pics[j], f"{stem}.png")
-            stems_all.extend(stems)
-            i0 += n
-        for png in (map_png, tree_png, image_png):
-            png.wait()
-            written.extend(png.written)
-    if args.out_root and len(names) != len(stems_all):
-        raise RuntimeError(f"--out-root: {len(names)} label names for {len(stems_all)} images")
-
-    M = len(stems_all)
+def _report(args, head, run, M):
+    """The tallies and counters of the whole split -> (report, selection.json)"""
+    nc, size, k, r = head.nc, head.size, run.k, run.r
     total = M * size[0] * size[1]
-    c = {name: v.cpu() for name, v in counters.items()}
+    c = {name: v.cpu() for name, v in run.counters.items()}
     selection = {"radius": k, "select_radius": r, "size": list(size), "kind": args.kind, "by": args.by,
-                 "budget": args.budget, "budget_pixels_per_image": budget_pixels, "seed": args.seed, "picks": per_stem}
+                 "budget": args.budget, "budget_pixels_per_image": run.budget_pixels, "seed": args.seed, "picks": run.per_stem}
 
     def summary(by, shown):
-        t = tallies[by]
+        t = run.tallies[by]
         return {"shown": shown, "shown_share": shown / total if total else 0.0, "picks": t["picks"],
                 "picks_per_image_mean": t["picks"] / max(1, M), "picks_per_image_max": t["picks_max"], "stops": t["stops"]}
 
@@ -358,78 +294,63 @@ def main(args):
               "kind": args.kind, "by": args.by, "radius": k, "select_radius": r, "size": list(size), "budget": args.budget,
               "budget_is": "per image: every image may show --budget x its own pixels (RIPU's protocol), unlike "
                            "acquire's ranking over the whole split",
-              "budget_pixels_per_image": budget_pixels, "max_picks": args.max_picks, "seed": args.seed, "images": M,
-              "total_pixels": total, "nonfinite": int(nonfinite.item()), "previous": args.previous,
+              "budget_pixels_per_image": run.budget_pixels, "max_picks": args.max_picks, "seed": args.seed, "images": M,
+              "total_pixels": total, "nonfinite": int(run.nonfinite.item()), "previous": args.previous,
               "kept": c["kept"].tolist(), "filled": c["filled"].tolist()}
     report.update(summary(args.by, int(c["shown"])))
-    if labelled:
-        if int(c["bad_targets"]):
-            raise RuntimeError(f"ripu: {int(c['bad_targets'])} target pixels are outside [0, {nc})")
+    if head.labelled:
+        annotated = ac.annotated_block("ripu", c, run.given, nc)
         wrong_all = int(c["wrong_all"])
         per = {args.by: dict(summary(args.by, int(c["shown"])), wrong_shown=int(c["wrong_shown"]))}
-        for by in others:
-            s = {name: int(v.item()) for name, v in side[by].items()}
+        for by in run.others:
+            s = {name: int(v.item()) for name, v in run.side[by].items()}
             per[by] = dict(summary(by, s["shown"]), wrong_shown=s["wrong_shown"])
         for v in per.values():
             v["error_recall"] = v["wrong_shown"] / wrong_all if wrong_all else 0.0
-        ann, giv = c["annotated"].tolist(), given.cpu().tolist()
         report.update(criteria=per, error_recall={by: v["error_recall"] for by, v in per.items()},
-                      error_recall_chosen=per[args.by]["error_recall"], wrong_pixels=wrong_all, annotated=ann,
-                      annotated_pixels=sum(ann), given=giv,
-                      annotated_share_per_class=[a / g if g else 0.0 for a, g in zip(ann, giv)])
-    for folder in (args.out_root, args.out):
-        if folder:
-            path = os.path.join(folder, "selection.json")
-            hc.write_json(selection, path)
-            written.append(path)
-    report["written"] = written
+                      error_recall_chosen=per[args.by]["error_recall"], wrong_pixels=wrong_all, **annotated)
+    return report, selection
+
+
+def main(args):
+    _refusals(args)
+    head = ac.open_head(args)
+    nc, size, dev, k = head.nc, head.size, head.dev, args.radius
+    before, before_radius = read_selection(args.previous, size) if args.previous else ({}, 0)
+    others = [by for by in CRITERIA if by != args.by] if head.labelled else []
+    run = SimpleNamespace(
+        k=k, r=k if args.select_radius is None else args.select_radius, before=before, before_radius=before_radius,
+        budget_pixels=int(math.floor(args.budget * size[0] * size[1])), others=others,
+        nonfinite=torch.zeros(1, dtype=torch.int64, device=dev), given=torch.zeros(nc, dtype=torch.int64, device=dev),
+        counters=new_apply_counters(nc, dev, APPLY_COUNTERS if head.labelled else ("shown", "kept", "filled")),
+        side={by: new_apply_counters(nc, dev, ("shown", "wrong_shown", "wrong_all")) for by in others},
+        tallies={by: {"picks": 0, "picks_max": 0, "stops": dict.fromkeys(STOPS, 0)} for by in [args.by] + others},
+        per_stem={})
+    with hc.png_pool() as pool:
+        writer = ac.LabelTreeWriter(pool, args, "--out-root", args.out_root, args.out)
+        for stems, images, target in ac.batches(args, head, pool):
+            _batch(args, head, run, writer, stems, images, target)
+        written = writer.close()
+    M, r = writer.seen, run.r
+    report, selection = _report(args, head, run, M)
     print(f"{report['dataset']} (task {args.task}): {M} images, {report['picks']} regions of radius {r} scored over radius {k} "
           f"by {args.by} ({args.kind}): {report['shown']} pixels shown ({report['shown_share'] * 100:.2f} % of the split; the "
-          f"budget is {budget_pixels} pixels PER IMAGE); {report['nonfinite']} non-finite pixels")
+          f"budget is {run.budget_pixels} pixels PER IMAGE); {report['nonfinite']} non-finite pixels")
     print("  images stopped: " + "  ".join(f"{name} {v}" for name, v in report["stops"].items()))
-    if labelled:
+    if head.labelled:
         print("  error recall at the budget: " + "  ".join(f"{by} {v * 100:.2f} %" for by, v in report["error_recall"].items()))
-    if written:
-        print(f"{len(written)} files written")
-    if args.json:
-        hc.write_json(report, args.json)
-    return report
+    return ac.finish(report, written, args, selection)
 
 
 def _refusals(args):
     """Raise a RuntimeError that names why this combination of flags is refused."""
-    if sum(bool(v) for v in (args.images, args.dataset, args.synthetic)) != 1:
-        raise RuntimeError("give one source of images: --images DIR, --dataset cityscapes|BDD|IDD or --synthetic N")
-    if min(args.height, args.width, args.batch_size) < 1 or args.synthetic < 0:
-        raise RuntimeError("sizes and --batch-size must be positive")
-    if args.height % 2 or args.width % 2:
-        raise RuntimeError("--height and --width must be even")
-    if args.height * args.width > _ripu_lib.MAX_IMAGE_PIXELS:
-        raise RuntimeError(f"--height {args.height} x --width {args.width}: at most 2^24 pixels per image")
-    if not (args.json or args.out or args.out_root):
-        raise RuntimeError("nothing to do: give --json FILE, --out DIR or --out-root ROOT")
-    if not 0.0 < args.budget <= 1.0:
-        raise RuntimeError(f"--budget {args.budget} outside (0, 1]: a share of every image's pixels")
+    ac.refuse_head(args, "every image's", _ripu_lib.MAX_IMAGE_PIXELS)
     check_radius("--radius", "radius", args.radius, _ripu_lib.MIN_RADIUS)
     if args.select_radius is not None:
         check_radius("--select-radius", "radius", args.select_radius, 0)
     if not 1 <= args.max_picks <= _ripu_lib.MAX_PICKS:
         raise RuntimeError(f"--max-picks {args.max_picks} outside [1, {_ripu_lib.MAX_PICKS}]")
-    if args.images and args.by == "oracle":
-        raise RuntimeError("--by oracle needs labels: give --dataset or --synthetic")
-    if args.out_root and args.images:
-        raise RuntimeError("--out-root writes what an annotator would answer: it needs labels (--dataset or --synthetic); "
-                           "with --images give --out DIR")
-    if bool(args.out_root) != bool(args.layout):
-        raise RuntimeError("--out-root and --layout cityscapes|BDD go together")
-    if args.out_root and args.dataset == "IDD":
-        raise RuntimeError("--out-root does not take --dataset IDD: its loaders remap level-3 ids, so the label "
-                           "files would need the inverse map")
-    if (args.previous_root or args.fill_root) and not args.out_root:
-        raise RuntimeError("--previous-root and --fill-root are label trees laid out as --out-root lays its own: they need "
-                           "--out-root and --layout")
-    if args.previous_root and not args.previous:
-        raise RuntimeError("--previous-root goes with --previous SEL.json, the selection that tree was written for")
+    ac.refuse_rounds(args)
 
 
 def build_parser():
@@ -437,29 +358,13 @@ def build_parser():
                                                  "per pixel from the (2k+1)^2 window centred on it, a greedy pick under "
                                                  "a per-image pixel budget, and the label tree an annotator of those "
                                                  "regions would hand back")
-    p.add_argument("--state", required=True, help="checkpoint written by the trainers (or by the reference)")
-    p.add_argument("--num-classes", type=int, nargs="+", required=True)
-    p.add_argument("--task", type=int, required=True, help="which task's decoder predicts")
-    p.add_argument("--images", help="folder of unlabelled .jpg / .png images (searched recursively)")
-    rc.add_data_flags(p, dataset_help="a labelled dataset instead: the run simulates the annotator",
-                      synthetic_help="N procedural images instead (labelled)")
-    p.set_defaults(subset="train")
-    p.add_argument("--budget", type=float, required=True, help="share of EVERY IMAGE's pixels that may be shown")
+    ac.add_source_flags(p, "share of EVERY IMAGE's pixels that may be shown")
     p.add_argument("--radius", type=int, default=16, help="k of the (2k+1)^2 score window, 1 to 32 (default %(default)s)")
     p.add_argument("--select-radius", type=int, help="r of the (2r+1)^2 region a pick takes, 0 (pixel mode) to 32 "
                                                      "(default: --radius, region mode)")
-    p.add_argument("--kind", choices=A.KINDS, default="entropy", help="the per-pixel uncertainty (default %(default)s)")
-    p.add_argument("--by", choices=CRITERIA, default="ripu", help="the criterion (default %(default)s)")
-    p.add_argument("--seed", type=int, default=0, help="of --by random (default %(default)s)")
+    ac.add_criterion_flags(p, A.KINDS, CRITERIA, "the criterion")
     p.add_argument("--max-picks", type=int, default=4096, help="picks per image at most, 1 to 65536 (default %(default)s)")
-    p.add_argument("--previous", help="an earlier round's selection.json: its regions are not picked or shown again")
-    p.add_argument("--previous-root", help="the label tree of that round: its labelled pixels are kept")
-    p.add_argument("--fill-root", help="a label tree (pseudo --out-root, say) for the pixels still empty")
-    p.add_argument("--json", help="write the report here")
-    p.add_argument("--out", help="write <stem>_select.png (255 selected, 128 kept, 64 filled) and <stem>_score.png "
-                                 "(key >> 24) here")
-    p.add_argument("--out-root", help="with labels: write a dataset tree the trainers open as --cs-datadir / --bdd-datadir")
-    p.add_argument("--layout", choices=("cityscapes", "BDD"), help="the tree --out-root writes")
+    ac.add_round_flags(p, "its regions are not picked or shown again", "<stem>_score.png (key >> 24)")
     return p
 
 

@@ -12,14 +12,15 @@ distance.  Everything after q is integer arithmetic and is asserted exactly, on 
 import functools
 import glob
 import json
-import os
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 from tests import acquire_reference as R
+from tests import annotate_cases as AC
 from tests import head_cases as HC
+from tests.annotate_cases import IGNORE, N_IMAGES, SENTINEL, SIZE, checkpoint, read_tree, synthetic_targets
 from tests.head_cases import CLASSES, SHAPES, nhwc
 
 pytestmark = pytest.mark.gpu
@@ -27,10 +28,8 @@ pytestmark = pytest.mark.gpu
 K = 17
 BIG = (3, 16, 48)
 SCALE = 8.0                                     # the trained regime: logits 8 times as far apart
-IGNORE = 255
 TILE = (4, 6)                                   # the tile of the shared runs: ragged on every shape but (3, 16, 48)
 HEAD_WG, HEAD_BLOCKS = 256, 768                 # acquire_head.hip: kHeadWG, kHeadMaxBlocks
-SENTINEL = torch.tensor([0xA5] * 8, dtype=torch.uint8).view(torch.int64)
 TILE_CASES = (((2, 2), (2, 12, 20)), ((2, 2), BIG), ((4, 6), (1, 9, 7)), ((4, 6), (2, 12, 20)), ((6, 4), (1, 9, 7)),
               ((6, 4), (2, 12, 20)), ((8, 8), BIG), ((256, 256), BIG), ((256, 256), (1, 1, 1)), ((2, 256), (2, 12, 20)))
 
@@ -347,28 +346,16 @@ def test_side_stream_gives_the_same_bytes(dev):
 
 
 # ---------------------------------------------------------------------------------- (7) apply
-def apply_maps(N, Hl, Wl, nc, seed):
-    g = torch.Generator().manual_seed(seed)
-    target = HC.make_target(nc, (N, Hl, Wl), IGNORE, seed)
-    previous = torch.randint(0, nc + 2, (N, Hl, Wl), generator=g, dtype=torch.uint8)
-    previous[torch.rand(N, Hl, Wl, generator=g) < 0.5] = 250
-    fill = torch.randint(0, nc + 2, (N, Hl, Wl), generator=g, dtype=torch.uint8)
-    fill[torch.rand(N, Hl, Wl, generator=g) < 0.3] = 250
-    return target, previous, fill
-
-
-@pytest.mark.parametrize("Wl", (1, 3, 5, 1001, 1024))
-@pytest.mark.parametrize("Hl", (1, 5))
+@pytest.mark.parametrize("Wl", AC.APPLY_WIDTHS)
+@pytest.mark.parametrize("Hl", AC.APPLY_HEIGHTS)
 def test_apply_maps_and_counters(dev, Hl, Wl):
     from mdil_ss_amd import acquire as A
-    nc, N = 20, 2
-    target, previous, fill = apply_maps(N, Hl, Wl, nc, seed=Hl * 2000 + Wl)
+    nc, N = AC.APPLY_NC, AC.APPLY_N
+    _, target, previous, fill, _ = AC.apply_maps(N, Hl, Wl, nc, AC.apply_seed(Hl, Wl))
     dmaps = [t.to(dev) for t in (target, previous, fill)]
-    for tile in ((2, 2), (4, 6)):
+    for tile in AC.APPLY_TILES:
         Ty, Tx = R.grid((Hl, Wl), tile)
-        g = torch.Generator().manual_seed(Wl)
-        sel = (torch.rand(N, Ty, Tx, generator=g) < 0.4).to(torch.uint8) * torch.randint(1, 256, (N, Ty, Tx), generator=g,
-                                                                                        dtype=torch.uint8)
+        sel = AC.tile_selection(N, (Ty, Tx), AC.apply_seed(Hl, Wl))
         dsel = sel.to(dev)
         for use in range(8):
             host = [m if use >> i & 1 else None for i, m in enumerate((target, previous, fill))]
@@ -381,11 +368,7 @@ def test_apply_maps_and_counters(dev, Hl, Wl):
                 what = (tile, use, times)
                 assert out.dtype == torch.uint8 and torch.equal(out.cpu(), want["out"]), what
                 assert mask.dtype == torch.uint8 and torch.equal(mask.cpu(), want["mask"]), what
-                assert int(counters["shown"]) == times * want["shown"], what
-                for k in ("kept", "filled") + (("annotated",) if host[0] is not None else ()):
-                    assert torch.equal(counters[k].cpu(), times * want[k]), (k, what)
-                if host[0] is not None:
-                    assert int(counters["bad_targets"]) == times * want["bad_targets"], what
+                AC.check_counters(counters, want, times)
     every = torch.ones(N, Ty, Tx, dtype=torch.uint8, device=dev)
     out, _ = A.acquire_apply(every, (Hl, Wl), tile, nc, dmaps[0], dmaps[1], dmaps[2], IGNORE, 250)
     assert torch.equal(out.cpu(), target)                             # every tile chosen: the target itself
@@ -398,7 +381,7 @@ def test_apply_null_outputs_refusals_and_guard_bands(dev, Wl):
     from mdil_ss_amd import _acquire_lib
     lib = _acquire_lib.load()
     nc, N, Hl, tile = 20, 2, 5, (4, 6)
-    target, previous, fill = apply_maps(N, Hl, Wl, nc, seed=Wl)
+    _, target, previous, fill, _ = AC.apply_maps(N, Hl, Wl, nc, AC.apply_seed(Hl, Wl))
     Ty, Tx = R.grid((Hl, Wl), tile)
     sel = (torch.arange(N * Ty * Tx).reshape(N, Ty, Tx) % 2).to(torch.uint8)
     want = R.apply_ref(sel, (Hl, Wl), tile, nc, target, previous, fill, IGNORE, 250)
@@ -418,15 +401,7 @@ def test_apply_null_outputs_refusals_and_guard_bands(dev, Wl):
         assert call(p) == 0, lib.mdil_acquire_last_error()
         torch.cuda.synchronize()
         arena.read()
-        arena.assert_untouched([k for k in given if k != "bad_targets" or want["bad_targets"]], given)
-        for k in ("out", "mask"):
-            if k in given:
-                assert torch.equal(arena.cut(k), want[k].reshape(-1)), (k, given)
-        for k in ("annotated", "kept", "filled"):
-            if k in given:
-                assert torch.equal(arena.cut(k).view(torch.int64) - SENTINEL, want[k]), (k, given)
-        if "shown" in given:
-            assert int(arena.cut("shown").view(torch.int64) - SENTINEL) == want["shown"]
+        AC.check_arena(arena, given, want, ("shown", "bad_targets"))
     arena = HC.Arena(dev, sizes)
     every = {k: arena.ptr(k) for k in sizes}
     for p, kw, text in ((dict.fromkeys(sizes), {}, b"nothing to write"), (every, dict(th=3), b"tile 3 x 6"),
@@ -439,16 +414,8 @@ def test_apply_null_outputs_refusals_and_guard_bands(dev, Wl):
 
 
 # ----------------------------------------------------------------------------- (8) end to end
-@pytest.fixture(scope="module")
-def checkpoint(dev, tmp_path_factory):
-    path = tmp_path_factory.mktemp("acquire") / "checkpoint.pth.tar"
-    HC.save_checkpoint(HC.tiny_model(dev), path)
-    return str(path)
-
-
-N_IMAGES, SIZE, CLI_TILE = 4, (64, 128), (16, 16)
-CLI = ["--num-classes", "20", "20", "--task", "1", "--synthetic", str(N_IMAGES), "--height", "64", "--width", "128",
-       "--batch-size", "3", "--subset", "val", "--tile", "16", "16"]
+CLI_TILE = (16, 16)
+CLI = AC.CLI_BASE + ["--subset", "val", "--tile", "16", "16"]
 REPORT_KEYS = ("dataset", "kind", "by", "tile", "budget", "images", "total_pixels", "pixels_asked", "pixels_spent",
                "tiles", "tiles_selected", "images_touched", "tiles_per_image_mean", "tiles_per_image_max",
                "mean_uncertainty_selected", "mean_uncertainty_all", "mean_impurity_selected", "mean_impurity_all",
@@ -456,15 +423,7 @@ REPORT_KEYS = ("dataset", "kind", "by", "tile", "budget", "images", "total_pixel
                "shown", "annotated", "annotated_pixels", "given", "annotated_share_per_class", "kept", "filled", "written")
 
 
-def synthetic_targets():
-    from mdil_ss_amd.dataset import ProceduralSeg
-    ds = ProceduralSeg(N_IMAGES, 64, 128, 20, seed=13, domain=1)
-    return torch.stack([ds[i][1][0] for i in range(N_IMAGES)]).to(torch.uint8)
-
-
-def run_cli(checkpoint, extra):
-    from mdil_ss_amd import acquire as A
-    return A.main(A.build_parser().parse_args(["--state", checkpoint] + CLI + [str(v) for v in extra]))
+run_cli = functools.partial(AC.run_cli, "acquire", CLI)
 
 
 def selected_mask(selection):
@@ -473,19 +432,6 @@ def selected_mask(selection):
         for y0, x0, y1, x1, _ in tiles:
             mask[int(stem[-4:]), y0:y1, x0:x1] = True
     return mask
-
-
-def read_tree(root, layout):
-    import numpy as np
-    from mdil_ss_amd import dataset as D
-    ds = (D.BDD100k if layout == "BDD" else D.cityscapes)(str(root), subset="val")
-    assert len(ds) == N_IMAGES and len(ds.filenamesGt) == N_IMAGES
-    maps = []
-    for i in range(N_IMAGES):
-        image, label = ds[i]
-        assert image.size == (128, 64)
-        maps.append(torch.from_numpy(np.array(label)))
-    return torch.stack(maps)
 
 
 @pytest.mark.parametrize("layout, by", (("BDD", "ripu"), ("cityscapes", "oracle")))
@@ -520,9 +466,8 @@ def test_cli_report_selection_and_label_tree(dev, checkpoint, tmp_path, layout, 
     import numpy as np
     from PIL import Image
     assert len(glob.glob(str(out / "*_select.png"))) == saved["images_touched"] == len(selection["tiles"])
+    AC.assert_select_maps(out, selection["tiles"], chosen)
     for stem in selection["tiles"]:
-        with Image.open(out / f"{stem}_select.png") as im:
-            assert torch.equal(torch.from_numpy(np.array(im)) == 255, chosen[int(stem[-4:])])
         with Image.open(out / f"{stem}_uncertainty.png") as im:
             assert np.array(im).shape == SIZE
     # the scores in selection.json are the criterion's, in rank order within an image
@@ -537,12 +482,7 @@ def test_cli_same_seed_same_bytes_and_previous_rounds(dev, checkpoint, tmp_path)
     for root in roots[:2]:
         run_cli(checkpoint, ["--budget", budget, "--by", "random", "--seed", 3, "--out-root", root, "--layout", "BDD",
                              "--json", root / "report.json"])
-    files = sorted(os.path.relpath(p, roots[0]) for p in glob.glob(str(roots[0] / "**" / "*"), recursive=True)
-                   if os.path.isfile(p))
-    assert len(files) == 2 * N_IMAGES + 2
-    for name in files:
-        if name != "report.json":                                     # the report lists the paths it wrote
-            assert open(roots[0] / name, "rb").read() == open(roots[1] / name, "rb").read(), name
+    AC.assert_same_files(roots[0], roots[1], 2 * N_IMAGES + 2)
     other = run_cli(checkpoint, ["--budget", budget, "--by", "random", "--seed", 4, "--json", tmp_path / "other.json"])
     with open(roots[0] / "selection.json") as f:
         first = json.load(f)
@@ -567,20 +507,13 @@ def test_cli_same_seed_same_bytes_and_previous_rounds(dev, checkpoint, tmp_path)
 
 
 def test_cli_on_unlabelled_images(dev, checkpoint, tmp_path):
-    import numpy as np
-    from PIL import Image
     root = tmp_path / "tree"
     run_cli(checkpoint, ["--budget", 0.1, "--by", "ripu", "--out-root", root, "--layout", "BDD"])   # writes the images
-    from mdil_ss_amd import acquire as A
-    args = ["--state", checkpoint, "--num-classes", "20", "20", "--task", "1", "--images", str(root / "images" / "val"),
-            "--height", "64", "--width", "128", "--batch-size", "3", "--tile", "16", "16", "--budget", "0.1", "--by", "ripu",
-            "--out", str(tmp_path / "plain"), "--json", str(tmp_path / "plain.json")]
-    plain = A.main(A.build_parser().parse_args(args))
+    plain = AC.run_cli("acquire", AC.images_base(root / "images" / "val"), checkpoint, [
+        "--tile", "16", "16", "--budget", "0.1", "--by", "ripu", "--out", tmp_path / "plain", "--json", tmp_path / "plain.json"])
     assert "error_recall" not in plain and "annotated" not in plain and plain["images"] == N_IMAGES
     assert 0 < plain["shown"] <= 0.1 * plain["total_pixels"] and plain["shown"] == plain["pixels_spent"]
     with open(tmp_path / "plain" / "selection.json") as f:
         selection = json.load(f)
     chosen = selected_mask(selection)
-    for stem in selection["tiles"]:
-        with Image.open(tmp_path / "plain" / f"{stem}_select.png") as im:
-            assert torch.equal(torch.from_numpy(np.array(im)) == 255, chosen[int(stem[-4:])])
+    AC.assert_select_maps(tmp_path / "plain", selection["tiles"], chosen)

@@ -24,6 +24,7 @@ import torch.nn.functional as F
 
 from tests import audit_reference as R
 from tests import head_cases as HC
+from tests.annotate_cases import checkpoint  # noqa: F401  (a fixture: the tiny model's checkpoint)
 from tests.head_cases import CLASSES, SHAPES, nhwc
 
 pytestmark = pytest.mark.gpu
@@ -530,13 +531,6 @@ def test_side_stream_gives_the_same_bytes(dev):
 @pytest.fixture(scope="module")
 def tiny_model(dev):
     return HC.tiny_model(dev)
-
-
-@pytest.fixture(scope="module")
-def checkpoint(tiny_model, tmp_path_factory):
-    path = tmp_path_factory.mktemp("audit") / "checkpoint.pth.tar"
-    HC.save_checkpoint(tiny_model, path)
-    return str(path)
 
 
 CLI = ["--num-classes", "20", "20", "--task", "1", "--synthetic", "2", "--height", "64", "--width", "128",

@@ -16,12 +16,13 @@ import os
 import pytest
 import torch
 
+from tests import annotate_cases as AC
 from tests import head_cases as HC
 from tests import ripu_reference as R
+from tests.annotate_cases import IGNORE, N_IMAGES, SENTINEL, SIZE, check_counters, checkpoint, read_tree, synthetic_targets
 
 pytestmark = pytest.mark.gpu
 
-IGNORE = 255
 # ripu.hip: a job of ripu_score is 32 output rows (kScoreRows) of a strip of 256 - 2k columns: 254 (k = 1), 250 (k = 3),
 # 192 (k = 32).  EDGES crosses the row segment at 32 and two strip borders of every radius (192 and 384; 250 and 500;
 # 254 and 508), with a last strip of a few columns.
@@ -31,7 +32,6 @@ RADII = (1, 3, 32)
 WIDTHS = (2, 20, 32)
 # ripu_select: chunks of 64 pixels up to 4096 of them, 128 beyond: the first size with chunks of 128
 WIDE = (1, 513, 512)
-SENTINEL = torch.tensor([0xA5] * 8, dtype=torch.uint8).view(torch.int64)
 
 
 @pytest.fixture(scope="module")
@@ -245,32 +245,12 @@ def test_select_with_chunks_of_128_pixels(dev):
 
 
 # ---------------------------------------------------------------------------------- (3) apply
-def apply_maps(N, Hl, Wl, nc, seed):
-    g = torch.Generator().manual_seed(seed)
-    shape = (N, Hl, Wl)
-    target = HC.make_target(nc, shape, IGNORE, seed)
-    previous = torch.where(torch.rand(shape, generator=g) < 0.4, torch.randint(0, nc + 2, shape, generator=g, dtype=torch.uint8),
-                           torch.tensor(250, dtype=torch.uint8))
-    fill = torch.where(torch.rand(shape, generator=g) < 0.6, torch.randint(0, nc + 2, shape, generator=g, dtype=torch.uint8),
-                       torch.tensor(250, dtype=torch.uint8))
-    label = torch.randint(0, nc, shape, generator=g, dtype=torch.uint8)
-    r = torch.rand(shape, generator=g)
-    sel = torch.where(r < 0.3, 255, torch.where(r < 0.5, 128, torch.where(r < 0.55, 1, 0))).to(torch.uint8)
-    return sel, target, previous, fill, label
-
-
-def check_counters(counters, want, times):
-    for k, v in counters.items():
-        w = want[k] if isinstance(want[k], torch.Tensor) else torch.tensor([want[k]])
-        assert torch.equal(v.cpu(), times * w), (k, times)
-
-
-@pytest.mark.parametrize("Wl", (1, 3, 5, 1001, 1024))
-@pytest.mark.parametrize("Hl", (1, 5))
+@pytest.mark.parametrize("Wl", AC.APPLY_WIDTHS)
+@pytest.mark.parametrize("Hl", AC.APPLY_HEIGHTS)
 def test_apply_maps_and_counters(dev, Hl, Wl):
     from mdil_ss_amd import ripu as P
-    nc, N = 20, 2
-    sel, target, previous, fill, label = apply_maps(N, Hl, Wl, nc, seed=Hl * 2000 + Wl)
+    nc, N = AC.APPLY_NC, AC.APPLY_N
+    sel, target, previous, fill, label = AC.apply_maps(N, Hl, Wl, nc, AC.apply_seed(Hl, Wl))
     ds, dt, dp, df, dl = (t.to(dev) for t in (sel, target, previous, fill, label))
     want = R.apply_ref(sel, nc, target, previous, fill, label, IGNORE, 250)
     counters = P.new_apply_counters(nc, dev)
@@ -380,7 +360,7 @@ def test_apply_null_outputs_refusals_and_guard_bands(dev, Wl):
     from mdil_ss_amd import ripu as P
     lib = _ripu_lib.load()
     nc, N, Hl = 20, 2, 5
-    sel, target, previous, fill, label = apply_maps(N, Hl, Wl, nc, seed=Wl)
+    sel, target, previous, fill, label = AC.apply_maps(N, Hl, Wl, nc, AC.apply_seed(Hl, Wl))
     want = R.apply_ref(sel, nc, target, previous, fill, label, IGNORE, 250)
     ds, dt, dp, df, dl = (t.to(dev) for t in (sel, target, previous, fill, label))
     npix = N * Hl * Wl
@@ -400,17 +380,7 @@ def test_apply_null_outputs_refusals_and_guard_bands(dev, Wl):
         assert call(p) == 0, lib.mdil_ripu_last_error()
         torch.cuda.synchronize()
         arena.read()
-        scalars = ("shown", "bad_targets", "wrong_shown", "wrong_all")
-        arena.assert_untouched([k for k in given if k not in scalars or want[k]], given)
-        for k in ("out", "mask"):
-            if k in given:
-                assert torch.equal(arena.cut(k), want[k].reshape(-1)), (k, given)
-        for k in ("annotated", "kept", "filled"):
-            if k in given:
-                assert torch.equal(arena.cut(k).view(torch.int64) - SENTINEL, want[k]), (k, given)
-        for k in scalars:
-            if k in given:
-                assert int(arena.cut(k).view(torch.int64) - SENTINEL) == want[k], (k, given)
+        AC.check_arena(arena, given, want, ("shown", "bad_targets", "wrong_shown", "wrong_all"))
     assert want["wrong_shown"] > 0 and want["wrong_all"] > want["wrong_shown"]
     assert want["bad_targets"] > 0 or npix < 100                              # 50 pixels hold no chosen target out of range
     arena = HC.Arena(dev, sizes)
@@ -428,31 +398,15 @@ def test_apply_null_outputs_refusals_and_guard_bands(dev, Wl):
 
 
 # ----------------------------------------------------------------------------- (5) end to end
-@pytest.fixture(scope="module")
-def checkpoint(dev, tmp_path_factory):
-    path = tmp_path_factory.mktemp("ripu") / "checkpoint.pth.tar"
-    HC.save_checkpoint(HC.tiny_model(dev), path)
-    return str(path)
-
-
-N_IMAGES, SIZE, RADIUS = 4, (64, 128), 4
-CLI = ["--num-classes", "20", "20", "--task", "1", "--synthetic", str(N_IMAGES), "--height", "64", "--width", "128",
-       "--batch-size", "3", "--subset", "val", "--radius", str(RADIUS)]
+RADIUS = 4
+CLI = AC.CLI_BASE + ["--subset", "val", "--radius", str(RADIUS)]
 REPORT_KEYS = ("dataset", "kind", "by", "radius", "select_radius", "budget", "budget_is", "budget_pixels_per_image", "images",
                "total_pixels", "shown", "shown_share", "picks", "picks_per_image_mean", "picks_per_image_max", "stops",
                "nonfinite", "criteria", "error_recall", "error_recall_chosen", "wrong_pixels", "annotated", "annotated_pixels",
                "given", "annotated_share_per_class", "kept", "filled", "written")
 
 
-def synthetic_targets():
-    from mdil_ss_amd.dataset import ProceduralSeg
-    ds = ProceduralSeg(N_IMAGES, 64, 128, 20, seed=13, domain=1)
-    return torch.stack([ds[i][1][0] for i in range(N_IMAGES)]).to(torch.uint8)
-
-
-def run_cli(checkpoint, extra):
-    from mdil_ss_amd import ripu as P
-    return P.main(P.build_parser().parse_args(["--state", checkpoint] + CLI + [str(v) for v in extra]))
+run_cli = functools.partial(AC.run_cli, "ripu", CLI)
 
 
 def selected_mask(selection):
@@ -464,19 +418,6 @@ def selected_mask(selection):
             mask[int(stem[-4:]), max(0, y - r):y + r + 1, max(0, x - r):x + r + 1] = True
             fresh += f
     return mask, fresh
-
-
-def read_tree(root, layout):
-    import numpy as np
-    from mdil_ss_amd import dataset as D
-    ds = (D.BDD100k if layout == "BDD" else D.cityscapes)(str(root), subset="val")
-    assert len(ds) == N_IMAGES and len(ds.filenamesGt) == N_IMAGES
-    maps_ = []
-    for i in range(N_IMAGES):
-        image, label = ds[i]
-        assert image.size == (128, 64)
-        maps_.append(torch.from_numpy(np.array(label)))
-    return torch.stack(maps_)
 
 
 @pytest.mark.parametrize("layout, by, select_radius", (("BDD", "ripu", None), ("cityscapes", "oracle", 0)))
@@ -530,12 +471,7 @@ def test_cli_same_seed_same_bytes_and_previous_rounds(dev, checkpoint, tmp_path)
     for root in roots[:2]:
         run_cli(checkpoint, ["--budget", budget, "--by", "random", "--seed", 3, "--out-root", root, "--layout", "BDD",
                              "--json", root / "report.json"])
-    files = sorted(os.path.relpath(p, roots[0]) for p in glob.glob(str(roots[0] / "**" / "*"), recursive=True)
-                   if os.path.isfile(p))
-    assert len(files) == 2 * N_IMAGES + 2
-    for name in files:
-        if name != "report.json":                                             # the report lists the paths it wrote
-            assert open(roots[0] / name, "rb").read() == open(roots[1] / name, "rb").read(), name
+    AC.assert_same_files(roots[0], roots[1], 2 * N_IMAGES + 2)
     with open(roots[0] / "selection.json") as f:
         first = json.load(f)
     other = run_cli(checkpoint, ["--budget", budget, "--by", "random", "--seed", 4, "--json", tmp_path / "other.json"])
@@ -564,22 +500,15 @@ def test_cli_same_seed_same_bytes_and_previous_rounds(dev, checkpoint, tmp_path)
 
 
 def test_cli_on_unlabelled_images(dev, checkpoint, tmp_path):
-    import numpy as np
-    from PIL import Image
-    from mdil_ss_amd import ripu as P
     root = tmp_path / "tree"
     run_cli(checkpoint, ["--budget", 0.1, "--by", "ripu", "--out-root", root, "--layout", "BDD"])   # writes the images
-    args = ["--state", checkpoint, "--num-classes", "20", "20", "--task", "1", "--images", str(root / "images" / "val"),
-            "--height", "64", "--width", "128", "--batch-size", "3", "--radius", str(RADIUS), "--budget", "0.1", "--by", "ripu",
-            "--out", str(tmp_path / "plain"), "--json", str(tmp_path / "plain.json")]
-    plain = P.main(P.build_parser().parse_args(args))
+    plain = AC.run_cli("ripu", AC.images_base(root / "images" / "val"), checkpoint, [
+        "--radius", RADIUS, "--budget", "0.1", "--by", "ripu", "--out", tmp_path / "plain", "--json", tmp_path / "plain.json"])
     assert "error_recall" not in plain and "annotated" not in plain and plain["images"] == N_IMAGES
     assert 0 < plain["shown"] <= 0.1 * plain["total_pixels"]
     with open(tmp_path / "plain" / "selection.json") as f:
         selection = json.load(f)
     chosen, fresh = selected_mask(selection)
     assert fresh == plain["shown"] == int(chosen.sum())
-    for stem in selection["picks"]:
-        with Image.open(tmp_path / "plain" / f"{stem}_select.png") as im:
-            assert torch.equal(torch.from_numpy(np.array(im)) == 255, chosen[int(stem[-4:])])
-        assert os.path.isfile(tmp_path / "plain" / f"{stem}_score.png")
+    AC.assert_select_maps(tmp_path / "plain", selection["picks"], chosen)
+    assert all(os.path.isfile(tmp_path / "plain" / f"{stem}_score.png") for stem in selection["picks"])
