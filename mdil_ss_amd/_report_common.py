@@ -5,7 +5,9 @@ workspace checks of the entry points, the workspace, source and bad-target steps
 label tree that audit, acquire and ripu write, and the flags and refusals of the command lines.  Plain
 functions; each takes the caller's name where a message carries it, so every message reads as it
 always did.  What only the annotator family (audit, acquire, ripu) shares -- its refusals and flags, the
-writer of that label tree, the annotated block of the report -- is one level up, in _annotate_common.py."""
+writer of that label tree, the annotated block of the report -- is one level up, in _annotate_common.py; what
+the label-size family (fullres, ensemble, boundary, segments, significance) shares -- the data at the labels' own
+size, its batch loop, the meters' prologue, its flags and refusals -- likewise, in _labelsize_common.py."""
 import os
 
 import torch
@@ -66,11 +68,20 @@ def meter_source(who, path, source, images_at, on_images, on_features, feat_name
     return fn, dev, N, H, W
 
 
-def refuse_bad_targets(who, tensors, nc, ignore_index):
-    bad = int(tensors["bad_targets"].item())
+def refuse_bad_pixels(who, nc, ignore_index, bad_targets, bad_preds=None):
+    """A meter's counts (int64 device tensors of one element) of the target pixels outside [0, nc) other than
+    the ignore index and, where it keeps one, of the predicted pixels outside [0, nc): either refuses."""
+    bad = int(bad_targets.item())
     if bad:
         raise RuntimeError(f"mdil {who}: {bad} target pixels are outside [0, {nc}) and are not the "
                            f"ignore index {ignore_index}")
+    bad = 0 if bad_preds is None else int(bad_preds.item())
+    if bad:
+        raise RuntimeError(f"mdil {who}: {bad} predicted pixels are outside [0, {nc})")
+
+
+def refuse_bad_targets(who, tensors, nc, ignore_index):
+    refuse_bad_pixels(who, nc, ignore_index, tensors["bad_targets"])
 
 
 # -------------------------------------------------------------------------------- command lines

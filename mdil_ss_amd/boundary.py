@@ -18,13 +18,14 @@ import functools
 import math
 import os
 
-import numpy as np
 import torch
 
 from . import _boundary_lib
 from . import _head_common as hc
+from . import _labelsize_common as ls
 from . import _report_common as rc
-from . import fullres as FR
+from ._labelsize_common import read_label_png  # noqa: F401  (public here)
+from .fullres import iou_rule
 
 _FN, _PATH = "boundary_count", "boundary"
 _chk = functools.partial(hc.chk, _FN, _PATH)
@@ -128,7 +129,7 @@ def score(counters, nc, ignore_index, widths):
     trimap mIoU -- the ``iouEval`` rule on the confusion matrices summed likewise --, then the
     interior mIoU (the last bin alone) and the ordinary mIoU (every bin).  Float64 on the host; the
     ignore class is left out exactly as ``fullres.ConfusionMeter.iou`` leaves it out."""
-    rule = functools.partial(FR.iou_rule, nc, ignore_index)
+    rule = functools.partial(iou_rule, nc, ignore_index)
     T, P, B = (counters[k].double().cumsum(1) for k in ("target_hist", "pred_hist", "both_hist"))
     conf = counters["confusion"].double()
     C = conf.cumsum(0)
@@ -172,21 +173,7 @@ class BoundaryMeter:
         ``add(model, images, task, target=t)`` / ``add(features, weight, bias, target=t)``, which first
         run ``fullres.fullres_head`` for the label map of ``target``'s size.
         -> (pred, dist_pred, dist_target); the distance maps are None without ``dist``."""
-        if len(source) == 2 and target is None:
-            pred, target = source
-        elif len(source) == 3 and target is not None:
-            if not isinstance(target, torch.Tensor) or target.dim() != 3:
-                raise RuntimeError("mdil BoundaryMeter.add: target must be a uint8 [N,H,W] device tensor")
-            fn = FR.predict_fullres if isinstance(source[0], torch.nn.Module) else FR.fullres_head
-            pred = fn(*source, tuple(target.shape[1:]))[0]
-        else:
-            raise RuntimeError("mdil BoundaryMeter.add: expects (pred, target), (model, images, task, target=...) or "
-                               "(features, weight, bias, target=...)")
-        _chk(pred, "pred", torch.uint8)
-        _chk(target, "target", torch.uint8)
-        if pred.dim() != 3 or pred.shape != target.shape:
-            raise RuntimeError(f"mdil BoundaryMeter.add: pred {tuple(pred.shape)} and target {tuple(target.shape)} "
-                               "must be uint8 [N,H,W] maps of one size")
+        (pred,), target = ls.label_maps(("BoundaryMeter", _FN, _PATH), source, target)
         N, H, W = pred.shape
         widths = self.widths if self.widths is not None else [ratio_width(self.ratio, H, W)]
         if not self.tensors:
@@ -208,10 +195,8 @@ class BoundaryMeter:
         if not self.tensors:
             shapes = counter_shapes(self.nc, self.nb)
             return {k: torch.zeros(shapes[k], dtype=torch.int64) for k in COUNTERS}
-        rc.refuse_bad_targets("BoundaryMeter", self.tensors, self.nc, self.ignore_index)
-        bad = int(self.tensors["bad_preds"].item())
-        if bad:
-            raise RuntimeError(f"mdil BoundaryMeter: {bad} predicted pixels are outside [0, {self.nc})")
+        rc.refuse_bad_pixels("BoundaryMeter", self.nc, self.ignore_index, self.tensors["bad_targets"],
+                             self.tensors["bad_preds"])
         return {k: self.tensors[k].cpu() for k in COUNTERS}
 
     def report(self):
@@ -238,63 +223,22 @@ def band_image(pred, target, dist_target, width):
     return img
 
 
-def read_label_png(folder, stem, shape):
-    """``<stem>_label.png`` of ``folder`` as u8 [H,W]; its size must be the label's."""
-    from PIL import Image
-    path = os.path.join(folder, f"{stem}_label.png")
-    if not os.path.isfile(path):
-        raise RuntimeError(f"--pred {folder}: {stem}_label.png not found")
-    with Image.open(path) as im:
-        arr = np.array(im)
-    if arr.ndim != 2 or arr.dtype != np.uint8:
-        raise RuntimeError(f"--pred {folder}: {stem}_label.png is not an 8-bit single-channel label map")
-    if arr.shape != tuple(shape):
-        raise RuntimeError(f"--pred {folder}: {stem}_label.png is {arr.shape[0]} x {arr.shape[1]}, its label "
-                           f"{shape[0]} x {shape[1]}")
-    return arr
-
-
 def main(args):
     _refusals(args)
     rc.refuse_task(args.task, args.num_classes)
-    if args.pred:
-        dev, nc, model = torch.device("cuda", 0), args.num_classes[args.task], None
-        torch.cuda.set_device(dev)
-    else:
-        dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
+    dev, nc, models, folders = ls.load_predictors(args)
     meter = BoundaryMeter(nc, nc - 1, widths=args.widths, ratio=None if args.widths else args.ratio)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
-    n_items, stems, sample = FR._open(args, nc)
+    data = ls.open_data(args, nc)
     with hc.png_pool() as pool:
         png = hc.PngWriter(pool, args.out)
-        for i0 in range(0, n_items, args.batch_size):
-            idx = range(i0, min(i0 + args.batch_size, n_items))
-            items = list(pool.map(sample, idx))
-            if model is not None:
-                images = hc.image_batch([im for im, _ in items], dev)
-                with torch.no_grad():
-                    feat = model.features(images, args.task).contiguous()
-                    w, b = (t.detach() for t in model.head_params(args.task))
-            maps = []
-            # one kernel call per run of images that share a native size
-            for s, e in FR._runs([lab.shape for _, lab in items]):
-                target = torch.from_numpy(np.stack([lab for _, lab in items[s:e]])).to(dev)
-                if model is not None:
-                    pred, _, dt = meter.add(feat[s:e], w, b, target=target, dist=bool(args.out))
-                else:
-                    read = [read_label_png(args.pred, stems[idx[k]], items[k][1].shape) for k in range(s, e)]
-                    pred, _, dt = meter.add(torch.from_numpy(np.stack(read)).to(dev), target, dist=bool(args.out))
-                if args.out:
-                    width = meter.widths[-1] if meter.widths is not None else ratio_width(meter.ratio, *target.shape[1:])
-                    maps.append((s, band_image(pred, target, dt, width).cpu().numpy()))
-            png.wait()                         # the batch before this one: bounds what is in flight
-            for s, img in maps:
-                for k in range(img.shape[0]):
-                    png.submit(img[k], f"{stems[idx[s + k]]}_boundary.png")
-        png.wait()
-    report = {"dataset": "synthetic" if args.synthetic else args.dataset, "task": args.task, "images": n_items,
-              "written": png.written}
+        for run in ls.label_runs(data, pool, dev, args.batch_size, models, args.task, folders, png):
+            pred, _, dt = meter.add(*run.sources, target=run.target, dist=bool(args.out))
+            if args.out:
+                width = meter.widths[-1] if meter.widths is not None else ratio_width(meter.ratio, *pred.shape[1:])
+                run.write("_boundary.png", band_image(pred, run.target, dt, width).cpu().numpy())
+    report = ls.report_header(args, data[0], png)
     report.update(meter.report())
     if args.score:
         shown = report["widths"] if meter.widths is not None else [f"{meter.ratio:g} of the diagonal"]
@@ -303,45 +247,31 @@ def main(args):
         for k, w in enumerate(shown):
             print(f"width {w}: boundary IoU {report['boundary_iou'][k]['mean'] * 100:.2f} %  trimap mIoU "
                   f"{report['trimap_iou'][k]['mean'] * 100:.2f} %")
-    if args.out:
-        print(f"{len(report['written'])} maps written to {args.out}")
-    if args.json:
-        hc.write_json(report, args.json)
-    return report
+    return hc.score_report(report, None, args)
 
 
 def _refusals(args):
     """Raise a RuntimeError that names why this combination of flags is refused."""
-    if not args.score and not args.out:
-        raise RuntimeError("nothing to do: give --score, --out DIR or both")
-    if args.json and not args.score:
-        raise RuntimeError("--json writes the score: it needs --score")
-    if args.pred and args.state:
-        raise RuntimeError("--pred scores maps already written and --state runs a checkpoint: give one of them")
-    if not args.pred and not args.state:
-        raise RuntimeError("give --state CHECKPOINT or --pred DIR")
+    ls.refuse_idle(args)
+    ls.refuse_json_without_score(args)
+    ls.refuse_sources(args)
     if args.widths is not None:
         check_widths(args.widths)
     elif not args.ratio > 0.0:
         raise RuntimeError("--ratio must be positive")
-    if not args.synthetic and not args.dataset:
-        raise RuntimeError("give --dataset cityscapes|BDD|IDD or --synthetic N")
-    if args.synthetic and args.dataset:
-        raise RuntimeError("--dataset and --synthetic exclude each other")
-    if min(args.height, args.width, args.batch_size, args.native_height, args.native_width) < 1:
-        raise RuntimeError("sizes and --batch-size must be positive")
+    ls.refuse_data(args)
 
 
 def build_parser():
-    p = FR.add_flags(hc.RefusingParser(_refusals, description="boundary IoU and trimap mIoU at the dataset's own size "
+    p = ls.add_flags(hc.RefusingParser(_refusals, description="boundary IoU and trimap mIoU at the dataset's own size "
                                                               "from a checkpoint or from label maps already written"),
-                     maps=False)
+                     label_maps=False, required=("num_classes", "task"), pred=True,
+                     out_help="write <stem>_boundary.png at the image's own size into this folder")
     g = p.add_mutually_exclusive_group()
     g.add_argument("--ratio", type=float, default=DEFAULT_RATIO,
                    help="band width as a share of the image diagonal, the published metric (default %(default)s)")
     g.add_argument("--widths", type=int, nargs="+", help="band widths in pixels instead: 1 to 8 increasing values up "
                                                          "to 128")
-    p.add_argument("--pred", help="score the <stem>_label.png files (train ids) of this folder instead of --state")
     return p
 
 

@@ -18,13 +18,12 @@ import functools
 import math
 import os
 
-import numpy as np
 import torch
 
 from . import _ensemble_lib
 from . import _head_common as hc
-from .fullres import ConfusionMeter, _open, _runs, add_flags, load_label_ids
-from .fullres import _refusals as _fullres_refusals
+from . import _labelsize_common as ls
+from .fullres import ConfusionMeter
 from .predict import default_palette
 
 MAX_VIEWS = _ensemble_lib.MAX_VIEWS
@@ -134,10 +133,30 @@ def scaled_size(size, scale):
     return max(8, 8 * int(math.floor(scale * size / 8 + 0.5)))
 
 
+def view_heads(sizes, flip):
+    """The hook of ``ls.label_runs`` for the ensemble: per input size (one sampler each) the batch's
+    images, plain and with ``flip`` mirrored, through the model -> cut(s, e): the one predictor's
+    (views of the items s .. e - 1, weight, bias)."""
+    def heads(models, task, images, dev):
+        (model,), views = models, []
+        with torch.no_grad():
+            for (h, w_), arrays in zip(sizes, images):
+                batch = hc.image_batch(arrays, dev)
+                for mirrored in ((False, True) if flip else (False,)):
+                    try:
+                        feat = model.features(batch.flip(3).contiguous() if mirrored else batch, task)
+                    except RuntimeError as e:
+                        raise RuntimeError(f"--scales: the eval forward refuses the {h} x {w_} input: {e}") from e
+                    views.append((feat.contiguous(), mirrored))
+            w, b = (t.detach() for t in model.head_params(task))
+        return lambda s, e: [([(f[s:e], m) for f, m in views], w, b)]
+    return heads
+
+
 def main(args):
     _refusals(args)
     dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
-    id_map = load_label_ids(args.label_ids, nc).to(dev) if args.label_ids else None
+    id_map = ls.load_label_ids(args.label_ids, nc).to(dev) if args.label_ids else None
     palette = default_palette(nc).contiguous().to(dev) if args.colour else None
     meter = EnsembleMeter(nc, nc - 1) if args.score else None
     if args.out:
@@ -148,52 +167,25 @@ def main(args):
     for h, w_ in sizes:
         a = copy.copy(args)
         a.height, a.width = h, w_
-        n_items, stems, sample = _open(a, nc)
+        n_items, stems, sample = ls.open_data(a, nc)
         samplers.append(sample)
     with hc.png_pool() as pool:
         png = hc.PngWriter(pool, args.out)
-        for i0 in range(0, n_items, args.batch_size):
-            idx = range(i0, min(i0 + args.batch_size, n_items))
-            jobs = [(k, i) for k in range(len(samplers)) for i in idx]
-            items = list(pool.map(lambda ki: samplers[ki[0]](ki[1]), jobs))
-            per_scale = [items[k * len(idx):(k + 1) * len(idx)] for k in range(len(samplers))]
-            labels = [lab for _, lab in per_scale[0]]
-            views = []
-            with torch.no_grad():
-                for (h, w_), batch in zip(sizes, per_scale):
-                    images = hc.image_batch([im for im, _ in batch], dev)
-                    for mirrored in ((False, True) if args.flip else (False,)):
-                        try:
-                            feat = model.features(images.flip(3).contiguous() if mirrored else images, args.task)
-                        except RuntimeError as e:
-                            raise RuntimeError(f"--scales: the eval forward refuses the {h} x {w_} input: {e}") from e
-                        views.append((feat.contiguous(), mirrored))
-                w, b = (t.detach() for t in model.head_params(args.task))
-            maps = []
-            # one kernel call per run of images that share a native size
-            for s, e in _runs([lab.shape for lab in labels]):
-                target = torch.from_numpy(np.stack(labels[s:e])).to(dev)
-                part = [(f[s:e], m) for f, m in views]
-                kw = dict(mode=args.mode, id_map=id_map, palette=palette, confidence=args.confidence)
-                if meter is not None:
-                    label, colour, conf = meter.add(part, w, b, target=target, **kw)
-                else:
-                    label, colour, conf = ensemble_head(part, w, b, tuple(target.shape[1:]), **kw)
-                if args.out:
-                    conf8 = None if conf is None else conf.mul(255.0).round_().to(torch.uint8).cpu().numpy()
-                    maps.append((s, label.cpu().numpy(), None if colour is None else colour.cpu().numpy(), conf8))
-            png.wait()                         # the batch before this one: bounds what is in flight
-            for s, label, colour, conf8 in maps:
-                for k in range(label.shape[0]):
-                    png.submit(label[k], f"{stems[idx[s + k]]}_label.png")
-                    if colour is not None:
-                        png.submit(colour[k], f"{stems[idx[s + k]]}_colour.png")
-                    if conf8 is not None:
-                        png.submit(conf8[k], f"{stems[idx[s + k]]}_conf.png")
-        png.wait()
-    report = {"dataset": "synthetic" if args.synthetic else args.dataset, "task": args.task, "images": n_items,
-              "written": png.written, "scales": [float(s) for s in args.scales], "flip": bool(args.flip),
-              "mode": args.mode}
+        for run in ls.label_runs((n_items, stems, samplers), pool, dev, args.batch_size, [model], args.task, png=png,
+                                 heads=view_heads(sizes, args.flip)):
+            (views, w, b), = run.sources
+            kw = dict(mode=args.mode, id_map=id_map, palette=palette, confidence=args.confidence)
+            if meter is not None:
+                label, colour, conf = meter.add(views, w, b, target=run.target, **kw)
+            else:
+                label, colour, conf = ensemble_head(views, w, b, tuple(run.target.shape[1:]), **kw)
+            if args.out:
+                conf8 = None if conf is None else conf.mul(255.0).round_().to(torch.uint8).cpu().numpy()
+                run.write("_label.png", label.cpu().numpy())
+                run.write("_colour.png", None if colour is None else colour.cpu().numpy())
+                run.write("_conf.png", conf8)
+    report = dict(ls.report_header(args, n_items, png), scales=[float(s) for s in args.scales], flip=bool(args.flip),
+                  mode=args.mode)
     what = "scales " + " / ".join(f"{s:g}" for s in args.scales) + (" + flip" if args.flip else "")
     return hc.score_report(report, meter, args, f", {what}, {args.mode}")
 
@@ -201,7 +193,7 @@ def main(args):
 def _refusals(args):
     """Raise a RuntimeError that names why this combination of flags is refused (before the GPU is
     touched): fullres's own refusals, then those of the ensemble's flags."""
-    _fullres_refusals(args)
+    ls.refuse_map_flags(args)
     scales = list(args.scales)
     if any(not (s > 0 and math.isfinite(s)) for s in scales):
         raise RuntimeError(f"--scales must be positive, got {scales}")
@@ -215,8 +207,9 @@ def _refusals(args):
 
 
 def build_parser():
-    p = add_flags(hc.RefusingParser(_refusals, description="multi-scale / flip ensemble: label maps and mIoU at the "
-                                                          "dataset's own size from a checkpoint"), " at scale 1")
+    p = ls.add_flags(hc.RefusingParser(_refusals, description="multi-scale / flip ensemble: label maps and mIoU at the "
+                                                             "dataset's own size from a checkpoint"),
+                     at_scale_1=" at scale 1")
     p.add_argument("--scales", type=float, nargs="+", default=[1.0],
                    help="one view per scale; the input is 8 * round(scale * size / 8) per axis")
     p.add_argument("--flip", action="store_true", help="every scale also mirrored")

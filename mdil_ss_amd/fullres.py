@@ -15,21 +15,16 @@ reports mIoU and per-class IoU by the reference's ``iouEval`` rule; ``--out`` wr
 ``<stem>_colour.png``.  ``--synthetic N --native-height Hn --native-width Wn`` does the same on the
 procedural dataset drawn at the native size."""
 import functools
-import json
 import os
 
-import numpy as np
 import torch
 
 from . import _fullres_lib
 from . import _head_common as hc
+from . import _labelsize_common as ls
+from . import _report_common as rc
+from ._labelsize_common import LABEL_IDS, load_label_ids, resize_image, synthetic_sample  # noqa: F401  (public here)
 from .predict import default_palette
-
-# train id -> the dataset's own label id, the ignore class (last) -> 0
-LABEL_IDS = {
-    "cityscapes": bytes((7, 8, 11, 12, 13, 17, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 31, 32, 33, 0)),
-}
-
 
 _FN, _PATH = "fullres_head", "full-resolution"
 _chk = functools.partial(hc.chk, _FN, _PATH)
@@ -106,10 +101,7 @@ class ConfusionMeter:
         index) was met."""
         if self.confusion is None:
             return torch.zeros(self.nc, self.nc, dtype=torch.int64)
-        bad = int(self.bad_targets.item())
-        if bad:
-            raise RuntimeError(f"mdil ConfusionMeter: {bad} target pixels are outside [0, {self.nc}) and are not the "
-                               f"ignore index {self.ignore_index}")
+        rc.refuse_bad_pixels("ConfusionMeter", self.nc, self.ignore_index, self.bad_targets)
         return self.confusion.cpu()
 
     def iou(self, matrix=None):
@@ -133,160 +125,33 @@ def iou_rule(nc, ignore_index, both, predicted, labelled):
 
 
 # ------------------------------------------------------------------------------------------ CLI
-def load_label_ids(spec, nc):
-    """``--label-ids``: a name in LABEL_IDS or a JSON file with one id per class -> u8 [nc] (host)."""
-    if spec in LABEL_IDS:
-        ids = list(LABEL_IDS[spec])
-    else:
-        if not os.path.isfile(spec):
-            raise RuntimeError(f"--label-ids {spec}: neither one of {sorted(LABEL_IDS)} nor a JSON file")
-        with open(spec) as f:
-            ids = json.load(f)
-    if not isinstance(ids, list) or len(ids) != nc or any(not isinstance(v, int) or not 0 <= v <= 255 for v in ids):
-        raise RuntimeError(f"--label-ids {spec}: expected {nc} integers in [0, 255]")
-    return torch.tensor(ids, dtype=torch.uint8)
-
-
-def resize_image(arr, height, width):
-    """uint8 [Hn,Wn,3] -> uint8 [height,width,3], PIL bilinear (the validation transform's image half)."""
-    from PIL import Image
-    return np.asarray(Image.fromarray(arr).resize((width, height), Image.BILINEAR), dtype=np.uint8)
-
-
-def synthetic_sample(ds, i, height, width):
-    """Item ``i`` of a ProceduralSeg drawn at the native size -> (image u8 [height,width,3] resized
-    for the network, label u8 [Hn,Wn] at the native size)."""
-    img, lab = ds[i]
-    u8 = img.mul(255.0).round_().to(torch.uint8).permute(1, 2, 0).contiguous().numpy()
-    return resize_image(u8, height, width), lab[0].to(torch.uint8).numpy()
-
-
-def _real_sample(ds, i, height, width, nc):
-    image, label = ds[i]                                   # PIL, both at their own size
-    lab = np.array(label, dtype=np.uint8)
-    lab[lab == 255] = nc - 1                               # the validation path's relabel
-    return resize_image(np.asarray(image.convert("RGB"), dtype=np.uint8), height, width), lab
-
-
-def _open(args, nc):
-    """-> (number of items, stems, sample(i) -> (image u8 [h,w,3], label u8 [Hn,Wn]))."""
-    if args.synthetic:
-        from .dataset import ProceduralSeg
-        ds = ProceduralSeg(args.synthetic, args.native_height, args.native_width, nc, seed=12 + args.task,
-                           domain=args.task)
-        return len(ds), [f"synthetic_{j:04d}" for j in range(len(ds))], \
-            lambda i: synthetic_sample(ds, i, args.height, args.width)
-    from .dataset import _ALIASES, _CLASSES
-    key = _ALIASES[args.dataset]
-    root = {"cityscapes": args.cs_datadir, "BDD": args.bdd_datadir, "IDD": args.idd_datadir}[key]
-    if not os.path.isdir(root):
-        raise RuntimeError(f"dataset root for {args.dataset} not found: {root} (set the datadir flag or run with "
-                           "--synthetic N)")
-    ds = _CLASSES[key](root, None, args.subset)            # co_transform=None: image AND label at their own size
-    stems = [os.path.splitext(os.path.basename(f))[0] for f in ds.filenames]
-    if len(set(stems)) != len(stems):
-        raise RuntimeError(f"image names under {root} are not unique: the outputs would collide")
-    return len(ds), stems, lambda i: _real_sample(ds, i, args.height, args.width, nc)
-
-
-def _runs(shapes):
-    """[(start, stop)] of the maximal runs of equal consecutive entries."""
-    out, i = [], 0
-    for j in range(1, len(shapes) + 1):
-        if j == len(shapes) or shapes[j] != shapes[i]:
-            out.append((i, j))
-            i = j
-    return out
-
-
 def main(args):
-    _refusals(args)
+    ls.refuse_map_flags(args)
     dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
     id_map = load_label_ids(args.label_ids, nc).to(dev) if args.label_ids else None
     palette = default_palette(nc).contiguous().to(dev) if args.colour else None
     meter = ConfusionMeter(nc, nc - 1) if args.score else None
     if args.out:
         os.makedirs(args.out, exist_ok=True)
-    n_items, stems, sample = _open(args, nc)
+    data = ls.open_data(args, nc)
     with hc.png_pool() as pool:
         png = hc.PngWriter(pool, args.out)
-        for i0 in range(0, n_items, args.batch_size):
-            idx = range(i0, min(i0 + args.batch_size, n_items))
-            items = list(pool.map(sample, idx))
-            images = hc.image_batch([im for im, _ in items], dev)
-            with torch.no_grad():
-                feat = model.features(images, args.task).contiguous()
-                w, b = (t.detach() for t in model.head_params(args.task))
-            maps = []
-            # one kernel call per run of images that share a native size
-            for s, e in _runs([lab.shape for _, lab in items]):
-                target = torch.from_numpy(np.stack([lab for _, lab in items[s:e]])).to(dev)
-                kw = dict(id_map=id_map, palette=palette)
-                if meter is not None:
-                    label, colour = meter.add(feat[s:e], w, b, target=target, **kw)
-                else:
-                    label, colour = fullres_head(feat[s:e], w, b, tuple(target.shape[1:]), **kw)
-                if args.out:
-                    maps.append((s, label.cpu().numpy(), None if colour is None else colour.cpu().numpy()))
-            png.wait()                         # the batch before this one: bounds what is in flight
-            for s, label, colour in maps:
-                for k in range(label.shape[0]):
-                    png.submit(label[k], f"{stems[idx[s + k]]}_label.png")
-                    if colour is not None:
-                        png.submit(colour[k], f"{stems[idx[s + k]]}_colour.png")
-        png.wait()
-    report = {"dataset": "synthetic" if args.synthetic else args.dataset, "task": args.task, "images": n_items,
-              "written": png.written}
-    return hc.score_report(report, meter, args)
-
-
-def _refusals(args):
-    """Raise a RuntimeError that names why this combination of flags is refused."""
-    if not args.score and not args.out:
-        raise RuntimeError("nothing to do: give --score, --out DIR or both")
-    if (args.colour or args.label_ids) and not args.out:
-        raise RuntimeError("--colour and --label-ids need --out DIR")
-    if args.json and not args.score:
-        raise RuntimeError("--json writes the score: it needs --score")
-    if not args.synthetic and not args.dataset:
-        raise RuntimeError("give --dataset cityscapes|BDD|IDD or --synthetic N")
-    if args.synthetic and args.dataset:
-        raise RuntimeError("--dataset and --synthetic exclude each other")
-    if min(args.height, args.width, args.batch_size, args.native_height, args.native_width) < 1:
-        raise RuntimeError("sizes and --batch-size must be positive")
-
-
-def add_flags(p, at_scale_1="", maps=True):
-    """The flags of this command line, which ``python -m mdil_ss_amd.ensemble`` shares;
-    ``maps=False``: those of ``python -m mdil_ss_amd.boundary``, which writes no label or colour map
-    and can score maps already written instead of running a checkpoint."""
-    from .dataset import add_datadir_flags
-    p.add_argument("--state", required=maps, help="checkpoint written by the trainers (or by the reference)")
-    p.add_argument("--num-classes", type=int, nargs="+", required=True)
-    p.add_argument("--task", type=int, required=True, help="which task's decoder predicts")
-    p.add_argument("--dataset", choices=("cityscapes", "BDD", "IDD"))
-    p.add_argument("--subset", default="val")
-    p.add_argument("--synthetic", type=int, default=0, help="N procedural images instead of a dataset")
-    p.add_argument("--native-height", type=int, default=1024, help="--synthetic: the labels' own height")
-    p.add_argument("--native-width", type=int, default=2048, help="--synthetic: the labels' own width")
-    p.add_argument("--height", type=int, default=512, help="the network's input height" + at_scale_1)
-    p.add_argument("--width", type=int, default=1024, help="the network's input width" + at_scale_1)
-    p.add_argument("--batch-size", type=int, default=6)
-    p.add_argument("--score", action="store_true", help="mIoU and per-class IoU against the full-size labels")
-    p.add_argument("--json", help="write the score (with the confusion matrix) here")
-    p.add_argument("--out", help="write <stem>_label.png at the image's own size into this folder" if maps else
-                   "write <stem>_boundary.png at the image's own size into this folder")
-    if maps:
-        p.add_argument("--colour", action="store_true", help="also write <stem>_colour.png")
-        p.add_argument("--label-ids", help=f"label PNGs in the dataset's own ids: one of {sorted(LABEL_IDS)} or a "
-                                           "JSON file with one id per class (default: train ids)")
-    add_datadir_flags(p)
-    return p
+        for run in ls.label_runs(data, pool, dev, args.batch_size, [model], args.task, png=png):
+            (feat, w, b), = run.sources
+            kw = dict(id_map=id_map, palette=palette)
+            if meter is not None:
+                label, colour = meter.add(feat, w, b, target=run.target, **kw)
+            else:
+                label, colour = fullres_head(feat, w, b, tuple(run.target.shape[1:]), **kw)
+            if args.out:
+                run.write("_label.png", label.cpu().numpy())
+                run.write("_colour.png", None if colour is None else colour.cpu().numpy())
+    return hc.score_report(ls.report_header(args, data[0], png), meter, args)
 
 
 def build_parser():
-    return add_flags(hc.RefusingParser(_refusals, description="label maps and mIoU at the dataset's own size from a "
-                                                             "checkpoint"))
+    return ls.add_flags(hc.RefusingParser(ls.refuse_map_flags, description="label maps and mIoU at the dataset's own "
+                                                                           "size from a checkpoint"))
 
 
 if __name__ == "__main__":

@@ -27,10 +27,9 @@ import numpy as np
 import torch
 
 from . import _head_common as hc
+from . import _labelsize_common as ls
 from . import _report_common as rc
 from . import _segments_lib
-from . import fullres as FR
-from .boundary import read_label_png
 
 _PATH = "segments"
 HISTS = ("segments", "pixels", "hit_pixels", "covered", "missed", "unjudged")
@@ -277,21 +276,7 @@ class SegmentMeter:
         run ``fullres.fullres_head`` for the label map of ``target``'s size.
         -> (pred, seen): ``seen`` = {"root", "area", "hit"} of the ground truth's segments (i32
         [N,H,W]) with ``overlap``, else None."""
-        if len(source) == 2 and target is None:
-            pred, target = source
-        elif len(source) == 3 and target is not None:
-            if not isinstance(target, torch.Tensor) or target.dim() != 3:
-                raise RuntimeError("mdil SegmentMeter.add: target must be a uint8 [N,H,W] device tensor")
-            fn = FR.predict_fullres if isinstance(source[0], torch.nn.Module) else FR.fullres_head
-            pred = fn(*source, tuple(target.shape[1:]))[0]
-        else:
-            raise RuntimeError("mdil SegmentMeter.add: expects (pred, target), (model, images, task, target=...) or "
-                               "(features, weight, bias, target=...)")
-        _chk("segments_label", pred, "pred")
-        _chk("segments_label", target, "target")
-        if pred.dim() != 3 or pred.shape != target.shape:
-            raise RuntimeError(f"mdil SegmentMeter.add: pred {tuple(pred.shape)} and target {tuple(target.shape)} "
-                               "must be uint8 [N,H,W] maps of one size")
+        (pred,), target = ls.label_maps(("SegmentMeter", "segments_label", _PATH), source, target)
         if not self.sides:
             self.sides = {s: new_counters(self.nc, self.nb, pred.device) for s in ("target", "pred")}
         need = workspace_bytes(*pred.shape)
@@ -315,13 +300,8 @@ class SegmentMeter:
         if not self.sides:
             shapes = counter_shapes(self.nc, self.nb)
             return {s: {k: torch.zeros(shapes[k], dtype=torch.int64) for k in COUNTERS} for s in ("target", "pred")}
-        bad = int(self.sides["target"]["bad_labels"].item())
-        if bad:
-            raise RuntimeError(f"mdil SegmentMeter: {bad} target pixels are outside [0, {self.nc}) and are not the "
-                               f"ignore index {self.ignore_index}")
-        bad = int(self.sides["pred"]["bad_labels"].item())
-        if bad:
-            raise RuntimeError(f"mdil SegmentMeter: {bad} predicted pixels are outside [0, {self.nc})")
+        rc.refuse_bad_pixels("SegmentMeter", self.nc, self.ignore_index, self.sides["target"]["bad_labels"],
+                             self.sides["pred"]["bad_labels"])
         return {s: {k: v.cpu() for k, v in c.items()} for s, c in self.sides.items()}
 
     def report(self):
@@ -356,43 +336,19 @@ def segment_image(target, seen, coverage, ignore_index):
 
 def _score_main(args):
     rc.refuse_task(args.task, args.num_classes)
-    if args.pred:
-        dev, nc, model = torch.device("cuda", 0), args.num_classes[args.task], None
-        torch.cuda.set_device(dev)
-    else:
-        dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
+    dev, nc, models, folders = ls.load_predictors(args)
     meter = SegmentMeter(nc, nc - 1, edges=args.edges, coverage=args.coverage, connectivity=args.connectivity)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
-    n_items, stems, sample = FR._open(args, nc)
+    data = ls.open_data(args, nc)
     with hc.png_pool() as pool:
         png = hc.PngWriter(pool, args.out)
-        for i0 in range(0, n_items, args.batch_size):
-            idx = range(i0, min(i0 + args.batch_size, n_items))
-            items = list(pool.map(sample, idx))
-            if model is not None:
-                images = hc.image_batch([im for im, _ in items], dev)
-                with torch.no_grad():
-                    feat = model.features(images, args.task).contiguous()
-                    w, b = (t.detach() for t in model.head_params(args.task))
-            maps = []
-            # one kernel call per run of images that share a native size
-            for s, e in FR._runs([lab.shape for _, lab in items]):
-                target = torch.from_numpy(np.stack([lab for _, lab in items[s:e]])).to(dev)
-                if model is not None:
-                    _, seen = meter.add(feat[s:e], w, b, target=target, overlap=bool(args.out))
-                else:
-                    read = [read_label_png(args.pred, stems[idx[k]], items[k][1].shape) for k in range(s, e)]
-                    _, seen = meter.add(torch.from_numpy(np.stack(read)).to(dev), target, overlap=bool(args.out))
-                if args.out:
-                    maps.append((s, segment_image(target, seen, meter.coverage, meter.ignore_index).cpu().numpy()))
-            png.wait()                         # the batch before this one: bounds what is in flight
-            for s, img in maps:
-                for k in range(img.shape[0]):
-                    png.submit(img[k], f"{stems[idx[s + k]]}_segments.png")
-        png.wait()
-    report = {"dataset": "synthetic" if args.synthetic else args.dataset, "task": args.task, "images": n_items,
-              "written": png.written}
+        for run in ls.label_runs(data, pool, dev, args.batch_size, models, args.task, folders, png):
+            _, seen = meter.add(*run.sources, target=run.target, overlap=bool(args.out))
+            if args.out:
+                run.write("_segments.png",
+                          segment_image(run.target, seen, meter.coverage, meter.ignore_index).cpu().numpy())
+    report = ls.report_header(args, data[0], png)
     report.update(meter.report())
     if args.score:
         def pct(v):
@@ -407,11 +363,7 @@ def _score_main(args):
             print(f"area {span}: segment recall {pct(report['segment_recall']['bins'][k])}  pixel recall "
                   f"{pct(report['pixel_recall']['bins'][k])}  segment precision "
                   f"{pct(report['segment_precision']['bins'][k])}")
-    if args.out:
-        print(f"{len(report['written'])} maps written to {args.out}")
-    if args.json:
-        hc.write_json(report, args.json)
-    return report
+    return hc.score_report(report, None, args)
 
 
 def read_map_png(path, name):
@@ -485,43 +437,28 @@ def _refusals(args):
         if not -1 <= args.keep_id <= 255 or not 0 <= args.fill <= 255:
             raise RuntimeError("--keep-id must be in [-1, 255] and --fill in [0, 255]")
         return
-    if not args.score and not args.out:
-        raise RuntimeError("nothing to do: give --score, --out DIR or both, or --clean DIR")
-    if args.json and not args.score:
-        raise RuntimeError("--json writes the score: it needs --score")
-    if args.pred and args.state:
-        raise RuntimeError("--pred scores maps already written and --state runs a checkpoint: give one of them")
-    if not args.pred and not args.state:
-        raise RuntimeError("give --state CHECKPOINT or --pred DIR")
+    ls.refuse_idle(args, ", or --clean DIR")
+    ls.refuse_json_without_score(args)
+    ls.refuse_sources(args)
     if args.num_classes is None or args.task is None:
         raise RuntimeError("scoring needs --num-classes and --task")
     check_edges(args.edges)
     check_coverage(args.coverage)
-    if not args.synthetic and not args.dataset:
-        raise RuntimeError("give --dataset cityscapes|BDD|IDD or --synthetic N")
-    if args.synthetic and args.dataset:
-        raise RuntimeError("--dataset and --synthetic exclude each other")
-    if min(args.height, args.width, args.batch_size, args.native_height, args.native_width) < 1:
-        raise RuntimeError("sizes and --batch-size must be positive")
+    ls.refuse_data(args)
 
 
 def build_parser():
-    p = FR.add_flags(hc.RefusingParser(_refusals, description="segment recall and precision by segment size at the "
+    p = ls.add_flags(hc.RefusingParser(_refusals, description="segment recall and precision by segment size at the "
                                                               "dataset's own size, and a despeckle filter for label "
                                                               "maps"),
-                     maps=False)
-    for action in p._actions:
-        if action.dest in ("num_classes", "task"):           # --clean goes without a model
-            action.required = False
-        if action.dest == "out":
-            action.help = ("--score: write <stem>_segments.png at the image's own size into this folder; --clean: the "
-                           "folder of the cleaned maps")
+                     label_maps=False, required=(), pred=True,      # --clean goes without a model
+                     out_help="--score: write <stem>_segments.png at the image's own size into this folder; --clean: "
+                              "the folder of the cleaned maps")
     p.add_argument("--edges", type=int, nargs="+", default=list(DEFAULT_EDGES),
                    help="area bins in pixels: 1 to 8 increasing values (default %(default)s)")
     p.add_argument("--coverage", default="0.5", help="share of a segment's judged pixels that must carry its label "
                                                      "for the segment to count as covered (default %(default)s)")
     p.add_argument("--connectivity", type=int, choices=(4, 8), default=8)
-    p.add_argument("--pred", help="score the <stem>_label.png files (train ids) of this folder instead of --state")
     p.add_argument("--clean", help="despeckle every 8-bit single-channel PNG under this folder into --out")
     p.add_argument("--min-area", type=int, default=16, help="--clean: segments of fewer pixels are removed "
                                                             "(default %(default)s)")

@@ -26,9 +26,9 @@ import numpy as np
 import torch
 
 from . import _head_common as hc
+from . import _labelsize_common as ls
 from . import _report_common as rc
 from . import _signif_lib
-from . import fullres as FR
 
 _PATH = "significance"
 MODES = {"bootstrap": _signif_lib.BOOTSTRAP, "jackknife": _signif_lib.JACKKNIFE, "swap": _signif_lib.SWAP}
@@ -263,16 +263,6 @@ class SignificanceMeter:
         self.counts = self.stray = None
         self.images, self.stems = 0, []
 
-    def _labels(self, source, target):
-        """One predictor's label map at ``target``'s size from what ``add`` was given for it."""
-        if isinstance(source, torch.Tensor):
-            return source
-        if isinstance(source, (tuple, list)) and len(source) == 3:
-            fn = FR.predict_fullres if isinstance(source[0], torch.nn.Module) else FR.fullres_head
-            return fn(*source, tuple(target.shape[1:]))[0]
-        raise RuntimeError("mdil SignificanceMeter.add: a predictor is a uint8 [N,H,W] label map, (model, images, "
-                           "task) or (features, weight, bias)")
-
     def add(self, *source, target=None, stems=None):
         """Unpaired: ``add(pred, target)`` with two u8 [N,H,W] label maps in train ids on the device,
         ``add(model, images, task, target=t)`` or ``add(features, weight, bias, target=t)``, which first
@@ -280,24 +270,7 @@ class SignificanceMeter:
         target=t)``, each of ``a`` and ``b`` a label map or such a triple.  ``stems``: the images'
         names for the influence list.  -> the label maps, one per predictor."""
         who = "SignificanceMeter.add"
-        if not self.paired and len(source) == 2 and target is None:
-            source, target = source[:1], source[1]
-        elif not self.paired and len(source) == 3 and target is not None:
-            source = (tuple(source),)
-        elif not (len(source) == self.G and target is not None):
-            raise RuntimeError(f"mdil {who}: expects " + (
-                "(a, b, target=...), each of a and b a label map, (model, images, task) or (features, weight, bias)"
-                if self.paired else
-                "(pred, target), (model, images, task, target=...) or (features, weight, bias, target=...)"))
-        if not isinstance(target, torch.Tensor) or target.dim() != 3:
-            raise RuntimeError(f"mdil {who}: target must be a uint8 [N,H,W] device tensor")
-        _chk("signif_count", target, "target")
-        preds = [self._labels(s, target) for s in source]
-        for p in preds:
-            _chk("signif_count", p, "pred")
-            if p.shape != target.shape:
-                raise RuntimeError(f"mdil {who}: pred {tuple(p.shape)} and target {tuple(target.shape)} must be uint8 "
-                                   "[N,H,W] maps of one size")
+        preds, target = ls.label_maps(("SignificanceMeter", "signif_count", _PATH), source, target, self.paired)
         N = target.shape[0]
         stems = [f"image_{self.images + i:06d}" for i in range(N)] if stems is None else [str(s) for s in stems]
         if len(stems) != N:
@@ -322,10 +295,7 @@ class SignificanceMeter:
         [0, nc) (other than the ignore index) was met."""
         if not self.images:
             raise RuntimeError("mdil SignificanceMeter: no image was added")
-        bad = int(self.stray[0].item())
-        if bad:
-            raise RuntimeError(f"mdil SignificanceMeter: {bad} target pixels are outside [0, {self.nc}) and are not "
-                               f"the ignore index {self.ignore_index}")
+        rc.refuse_bad_pixels("SignificanceMeter", self.nc, self.ignore_index, self.stray[0])
         return self.counts[:self.images].contiguous()
 
     def report(self, replicates=10000, seed=0, level=0.95, influence=10):
@@ -372,47 +342,19 @@ def _interval(row):
 
 
 def main(args):
-    from .boundary import read_label_png
     _refusals(args)
-    models, folders = [], []
-    if args.pred:
-        dev, nc = torch.device("cuda", 0), args.num_classes[args.task]
-        torch.cuda.set_device(dev)
-        folders = [args.pred] + ([args.pred_b] if args.pred_b else [])
-    elif args.state:
-        dev, nc, model = hc.load_model(args.state, args.num_classes, args.task)
-        models = [model]
-    else:
+    if args.before:
         dev, nc, before = hc.load_model(args.before, args.before_num_classes, args.task)
-        models = [before, hc.load_model(args.after, args.after_num_classes, args.task)[2]]
+        models, folders = [before, hc.load_model(args.after, args.after_num_classes, args.task)[2]], []
+    else:
+        dev, nc, models, folders = ls.load_predictors(args)
+        folders += [args.pred_b] if args.pred_b else []
     paired = len(models) + len(folders) == 2
     meter = SignificanceMeter(nc, nc - 1, paired=paired)
-    n_items, stems, sample = FR._open(args, nc)
+    data = ls.open_data(args, nc)
     with hc.png_pool() as pool:
-        for i0 in range(0, n_items, args.batch_size):
-            idx = range(i0, min(i0 + args.batch_size, n_items))
-            items = list(pool.map(sample, idx))
-            heads = []
-            if models:
-                images = hc.image_batch([im for im, _ in items], dev)
-                with torch.no_grad():
-                    for m in models:
-                        heads.append((m.features(images, args.task).contiguous(),
-                                      *(t.detach() for t in m.head_params(args.task))))
-            # one kernel call per run of images that share a native size
-            for s, e in FR._runs([lab.shape for _, lab in items]):
-                target = torch.from_numpy(np.stack([lab for _, lab in items[s:e]])).to(dev)
-                sources = [(feat[s:e], w, b) for feat, w, b in heads]
-                for folder in folders:
-                    read = [read_label_png(folder, stems[idx[j]], items[j][1].shape) for j in range(s, e)]
-                    sources.append(torch.from_numpy(np.stack(read)).to(dev))
-                names = [stems[idx[j]] for j in range(s, e)]
-                if paired:
-                    meter.add(*sources, target=target, stems=names)
-                elif models:
-                    meter.add(*sources[0], target=target, stems=names)
-                else:
-                    meter.add(sources[0], target, stems=names)
+        for run in ls.label_runs(data, pool, dev, args.batch_size, models, args.task, folders):
+            meter.add(*run.sources, target=run.target, stems=run.stems)
     report = {"dataset": "synthetic" if args.synthetic else args.dataset, "task": args.task}
     report.update(meter.report(replicates=args.replicates, seed=args.seed, level=args.level,
                                influence=args.influence))

@@ -159,12 +159,6 @@ def test_label_ids_from_a_file(tmp_path):
         F.load_label_ids(str(f), 27)
 
 
-def test_runs_of_equal_sizes():
-    from mdil_ss_amd.fullres import _runs
-    assert _runs([(2, 3)]) == [(0, 1)]
-    assert _runs([(2, 3), (2, 3), (4, 3), (2, 3), (2, 3), (2, 3)]) == [(0, 2), (2, 3), (3, 6)]
-
-
 def test_resize_is_pil_bilinear():
     from PIL import Image
     from mdil_ss_amd import fullres as F
