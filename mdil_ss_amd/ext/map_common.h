@@ -16,6 +16,8 @@
 //   route      kLog2e, is_finite, stage_parity, parity_logits
 //   ripu       u64, Run, load_bytes, store_bytes, flush_counters, kApplyFlushEvery, annotate_pixel, zero_annotator,
 //              flush_annotator (no head code)
+//   spx        u64, cached_add, flush_cache, Run, load_bytes, store_bytes, flush_counters, kApplyFlushEvery, annotate_pixel,
+//              zero_annotator, flush_annotator (no head code)
 // What differs on purpose stays in its file, where a comment says why: the three quantise rules and code16, each
 // file's wave_merged_add(s), route's fold_rows, pseudo_head's logits4 chain and its load_item.
 #pragma once
