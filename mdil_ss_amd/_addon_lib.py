@@ -1,6 +1,6 @@
-"""The loader the seventeen add-ons' ctypes bindings (_predict_lib, _fullres_lib, _ensemble_lib,
+"""The loader the add-ons' ctypes bindings (_predict_lib, _fullres_lib, _ensemble_lib,
 _drift_lib, _calib_lib, _tsne_lib, _similarity_lib, _boundary_lib, _pseudo_lib, _route_lib, _segments_lib, _refine_lib,
-_signif_lib, _openset_lib, _audit_lib, _acquire_lib, _ripu_lib) share.  Like the training library they have NO fallback: if a library is missing or
+_signif_lib, _openset_lib, _audit_lib, _acquire_lib, _ripu_lib, _spx_lib, _density_lib) share.  Like the training library they have NO fallback: if a library is missing or
 an entry point fails, a RuntimeError is raised.  (_lib.py, the training library's binding, keeps its
 own loader: it belongs to the build id.)"""
 import ctypes as C

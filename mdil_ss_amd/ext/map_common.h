@@ -18,6 +18,8 @@
 //              flush_annotator (no head code)
 //   spx        u64, cached_add, flush_cache, Run, load_bytes, store_bytes, flush_counters, kApplyFlushEvery, annotate_pixel,
 //              zero_annotator, flush_annotator (no head code)
+//   density    u64, is_finite, order_key16, wave_sum_u32, stage_parity, parity_logits, quad_bytes, cached_add_probed,
+//              flush_cache (and of head_common.h: vote, shape_ok, classes_ok, bounded_grid, launched)
 // What differs on purpose stays in its file, where a comment says why: the three quantise rules and code16, each
 // file's wave_merged_add(s), route's fold_rows, pseudo_head's logits4 chain and its load_item.
 #pragma once
@@ -34,6 +36,14 @@ constexpr int kPerItem = 8;                          // pixels a lane of a map k
 constexpr uint32_t kEmptySlot = 0xffffffffu;         // cached_add: no key; keys are below 2^31
 
 __device__ __forceinline__ bool is_finite(float v) { return fabsf(v) < INFINITY; }   // false for a NaN
+
+// The 16-bit code of a score (include/mdil_openset.h): the high half of the radix-sort key of its bits, order-preserving
+// over all floats (NaNs aside).  openset_head.hip keeps its own spelling, code16; density_head.hip uses this one.
+__device__ __forceinline__ uint32_t order_key16(float u) {
+  const uint32_t bits = __float_as_uint(u);
+  const uint32_t key = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+  return key >> 16;
+}
 
 // Sum over the 64 lanes of a wave, every lane active.  Values below 2^26: the sum fits.
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
@@ -96,6 +106,24 @@ __device__ __forceinline__ void cached_add(u64* __restrict__ table, uint32_t* ta
     atomicAdd(&counts[h], n);
   else
     __hip_atomic_fetch_add(table + slot, (u64)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// cached_add that tries PROBES slots (h, h ^ 1, ...) before the add goes to global memory; flush_cache serves both.
+template <int SLOTS, int PROBES>
+__device__ __forceinline__ void cached_add_probed(u64* __restrict__ table, uint32_t* tags, uint32_t* counts,
+                                                  uint32_t slot, uint32_t n) {
+  static_assert(SLOTS > 1 && (SLOTS & (SLOTS - 1)) == 0 && PROBES >= 1 && PROBES <= SLOTS, "the hash keeps log2(SLOTS) bits");
+  const uint32_t h = (slot * 2654435761u) >> (32 - __builtin_ctz(SLOTS));
+#pragma unroll
+  for (uint32_t probe = 0; probe < (uint32_t)PROBES; ++probe) {
+    const uint32_t hh = h ^ probe;
+    const uint32_t old = atomicCAS(&tags[hh], kEmptySlot, slot);
+    if (old == kEmptySlot || old == slot) {
+      atomicAdd(&counts[hh], n);
+      return;
+    }
+  }
+  __hip_atomic_fetch_add(table + slot, (u64)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // The occupied entries -> the global table, by the whole work-group of WG lanes, and the table is empty again;
